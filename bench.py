@@ -22,6 +22,12 @@ Implementations (``--impl``):
 
 Every timed step does the full work: input normalisation from uint8, forward, loss,
 backward, gradient all-reduce (N>1) and the SGD-momentum update.
+
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON line (``ms_per_step`` is
+the time of one timed step). ``--dump-outputs DIR`` then writes what the last timed step computed
+as ``DIR/<name>.npy`` so that two builds can be compared output for output (the inputs and the
+initial weights are seeded: identical from run to run). ``--full`` is where secondary
+measurements belong; there are none today.
 """
 from __future__ import annotations
 
@@ -85,6 +91,14 @@ def parse_args(argv=None):
     p.add_argument("--mds-samples", type=int, default=0, help="samples per rank written for --data mds "
                    "(default: enough for warmup + steps, at least 8 batches)")
     p.add_argument("--json-out", default=None)
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last step left for its caller (logits, the metric "
+                        "accumulators, parameters, gradients) as DIR/<name>.npy, float32 / float64, at most 64 MB "
+                        "(large arrays: a fixed seeded sample); same arguments -> same inputs, run to run")
+    p.add_argument("--full", action="store_true",
+                   help="also run the benchmark's secondary measurements; a plain run does only what the headline "
+                        "figure needs (set up, warm up, time --steps steps). Nothing is secondary today: every "
+                        "other measurement is a run of its own (--impl torch, --preset, --data mds, --gpus N)")
     p.add_argument("--phase-timeout", type=float, default=300.0,
                    help="world > 1: watchdog bound (s) on every phase (setup / warm-up / timed / checks); exit 75")
     p.add_argument("--comm-fallback", type=int, default=1, choices=[0, 1],
@@ -237,6 +251,50 @@ def _replica_tensors(step):
     return [p.detach() for p in getattr(step, "model").parameters()]
 
 
+DUMP_MAX_ELEMS = 3 << 20  # per array: 12 MiB of float32, so the four arrays of a step stay under 64 MB
+DUMP_SAMPLE_SEED = 20240611
+
+
+def step_outputs(step) -> dict:
+    """What the last step left for its caller, by name. Native: the head's logits of the last batch, the
+    metric accumulators (loss sum and correct count over every step since set-up), the flat fp32
+    parameters after the update and, without ZeRO, the flat gradient that update used (under ZeRO a
+    rank only holds its reduced shard). Torch impl: logits, loss, parameters, gradients."""
+    tr = getattr(step, "trainer", None)
+    if tr is not None:
+        tr.sync_master()  # ZeRO: every rank's shard of the master (collective; a no-op otherwise)
+        out = {"logits": tr.prog.logits, "loss_sum_correct": tr.prog.metrics[:2], "params": tr.prog.master}
+        if tr.zero is None:
+            out["grads"] = tr.prog.grad
+        return out
+    ps = [p for p in step.model.parameters()]
+    return {"logits": step.logits, "loss": step.loss.reshape(1),
+            "params": torch.cat([p.detach().reshape(-1) for p in ps]),
+            "grads": torch.cat([p.grad.reshape(-1) for p in ps if p.grad is not None])}
+
+
+def dump_outputs(step, info, out_dir: str) -> None:
+    """``--dump-outputs``: rank 0 writes ``step_outputs`` as ``<out_dir>/<name>.npy`` (float64 stays
+    float64, everything else becomes float32). An array of more than ``DUMP_MAX_ELEMS`` elements is
+    sampled at fixed positions (sorted draws of a seeded generator, the same for every run and build)."""
+    import numpy as np
+    outs = step_outputs(step)  # on every rank: may hold a collective
+    if info.device.type == "cuda":
+        torch.cuda.synchronize()
+    if info.rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outs.items():
+        t = t.detach()
+        if t.numel() > DUMP_MAX_ELEMS:
+            t = t.reshape(-1)
+            rng = np.random.default_rng(DUMP_SAMPLE_SEED)
+            idx = np.sort(rng.integers(0, t.numel(), size=DUMP_MAX_ELEMS, dtype=np.int64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _measure(args, info, wd, build_step, ddist, fault):
     """Build the step, warm up, check the replicas, time ``args.steps`` steps, check again.
     Returns (rc, elapsed seconds (max over ranks), meta); rc 4 = replicas diverged."""
@@ -296,6 +354,8 @@ def _measure(args, info, wd, build_step, ddist, fault):
     if not replicas_in_sync(step, info, "the timed steps", wd):
         release()
         return 4, 0.0, meta
+    if args.dump_outputs:
+        dump_outputs(step, info, args.dump_outputs)
     return 0, elapsed, meta
 
 

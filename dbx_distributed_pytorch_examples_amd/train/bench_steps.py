@@ -46,6 +46,7 @@ def build_torch_step(args, info) -> Tuple[Callable[[], None], Dict]:
         opt.zero_grad(set_to_none=True)
         loss.backward()
         opt.step()
+        step.logits, step.loss = out.detach(), loss.detach()  # bench.py --dump-outputs
 
     step.model = model  # bench.py replica check
     return step, {"memory_format": "channels_last" if args.channels_last else "nchw",

@@ -153,6 +153,37 @@ def test_diverged_one_graph_step_is_remeasured_on_c10d(monkeypatch, capsys, engi
     assert bench.main(["--steps", "1", "--warmup", "0", "--preset", "resnet18_cifar10"]) == 4 and calls == [1]
 
 
+def test_dump_outputs_is_repeatable_and_steps_are_timed(tmp_path, capsys, monkeypatch, engine):
+    """--dump-outputs writes the last step's outputs as float32 / float64 .npy under 64 MB, identical
+    from run to run with the same arguments (CPU reference ops are deterministic); --steps sets the
+    number of timed steps (the loss accumulator grows with it) and ms_per_step is the time of one;
+    --full is accepted and changes nothing of the line's meaning."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    engine()
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1 << 16)  # resnet18's 11 M parameters: the sampled path
+    base = ["--gpus", "1", "--preset", "resnet18_cifar10", "--batch", "4", "--warmup", "1"]
+    lines = []
+    for name, extra in (("a", ["--steps", "2"]), ("b", ["--steps", "2", "--full"]), ("c", ["--steps", "3"])):
+        assert bench.main(base + extra + ["--dump-outputs", str(tmp_path / name)]) == 0
+        lines.append(_line(capsys.readouterr().out))
+    a, b, c = ({f[:-4]: np.load(tmp_path / n / f) for f in sorted(os.listdir(tmp_path / n))} for n in "abc")
+    assert set(a) == {"logits", "loss_sum_correct", "params", "grads"}
+    assert a["logits"].shape == (4, 10) and a["params"].shape == a["grads"].shape == (1 << 16,)
+    assert a["loss_sum_correct"].dtype == np.float64 and a["logits"].dtype == a["params"].dtype == np.float32
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) < 64e6
+    for k in a:
+        assert np.isfinite(a[k]).all() and np.array_equal(a[k], b[k]), k
+    assert np.abs(a["grads"]).max() > 0 and np.abs(a["logits"]).max() > 0
+    # 1 warm-up + 2 / 3 timed steps of 4 images at a loss near ln(10) each
+    assert c["loss_sum_correct"][0] > a["loss_sum_correct"][0] > 3 * 4 * 1.0
+    assert not np.array_equal(a["params"], c["params"])
+    for d, steps in zip(lines, (2, 2, 3)):
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["unit"] == "images/s" and d["dtype"] == "bf16"
+        assert d["value"] == pytest.approx(4 * 1000.0 / d["ms_per_step"], rel=1e-3) and d["higher_is_better"] is True
+
+
 def test_torchrun_teardown_takes_the_supervised_children_along():
     """When torchrun tears the group down (here: SIGTERM to the whole launcher), no supervised rank
     child may survive it: the supervisors kill their children's process groups on SIGTERM and the
