@@ -56,6 +56,7 @@ int dbx_sgd(float*, const float*, float*, bf16*, long long, const float*, float,
             const float*, float, hipStream_t);
 int dbx_adam(float*, const float*, float*, float*, bf16*, long long, const float*, float, float, float, float, float, int,
              float, float, const float*, float, hipStream_t);
+int dbx_grad_accum(float*, const float*, long long, int, const float*, hipStream_t);
 int dbx_sumsq(const float*, long long, double*, hipStream_t);
 int dbx_lars_scale(const float*, float*, const int*, const int*, const int*, int, int, double*, float, float, float,
                    hipStream_t);
@@ -313,6 +314,9 @@ PYBIND11_MODULE(_C, m) {
     check(dbx_lars_scale(P<const float*>(p), P<float*>(g), P<const int*>(off), P<const int*>(len),
                          P<const int*>(adapt), nseg, max_len, P<double*>(norms), gs, eta, wd, S(st)),
           "lars_scale");
+  });
+  m.def("grad_accum", [](uintptr_t dst, uintptr_t src, long long n, int first, uintptr_t flag, uintptr_t st) {
+    check(dbx_grad_accum(P<float*>(dst), P<const float*>(src), n, first, P<const float*>(flag), S(st)), "grad_accum");
   });
   m.def("sumsq", [](uintptr_t x, long long n, uintptr_t out, uintptr_t st) {
     check(dbx_sumsq(P<const float*>(x), n, P<double*>(out), S(st)), "sumsq");

@@ -836,6 +836,26 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   }
 }
 
+// Gradient accumulation over the flat fp32 gradient: dst = first ? src : dst + src. ``flag`` (device,
+// nullable) overrides ``first`` at run time (first = flag[0] != 0), so one captured micro-step serves
+// every position of an accumulation window; in first mode dst is never read (stale NaN / Inf in the
+// accumulator cannot leak, and no memset is needed). 16 B per lane when both pointers are 16-byte
+// aligned; scalar otherwise (any 4-byte aligned slice is valid) and for the n % 4 tail.
+__global__ void grad_accum_kernel(float* __restrict__ dst, const float* __restrict__ src, long long n, int first,
+                                  const float* __restrict__ flag) {
+  if (flag) first = flag[0] != 0.f;
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long nth = (long long)gridDim.x * blockDim.x;
+  const bool vec = ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15) == 0;
+  const long long n4 = vec ? n / 4 : 0;
+  for (long long i = tid; i < n4; i += nth) {
+    f32x4 s = *reinterpret_cast<const f32x4*>(src + i * 4);
+    if (!first) s = *reinterpret_cast<const f32x4*>(dst + i * 4) + s;
+    *reinterpret_cast<f32x4*>(dst + i * 4) = s;
+  }
+  for (long long k = n4 * 4 + tid; k < n; k += nth) dst[k] = first ? src[k] : dst[k] + src[k];
+}
+
 // sum of squares over a flat fp32 buffer (global-norm clipping), one fp64 atomic per block. fp64
 // sums of fp32 block partials are exact (hence independent of block order) while the partials'
 // magnitudes span less than ~2^29; beyond that the last bits of the norm can depend on the order.
@@ -1223,6 +1243,12 @@ extern "C" int dbx_lars_scale(const float* p, float* g, const int* seg_off, cons
   hipLaunchKernelGGL(lars_norms_kernel, dim3(bx, nseg), dim3(256), 0, st, p, g, seg_off, seg_len, gs, norms);
   hipLaunchKernelGGL(lars_apply_kernel, dim3(bx, nseg), dim3(256), 0, st, p, g, seg_off, seg_len, adapt, norms, gs,
                      eta, wd);
+  RET_LAST;
+}
+extern "C" int dbx_grad_accum(float* dst, const float* src, long long n, int first, const float* flag,
+                              hipStream_t st) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(grad_accum_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, dst, src, n, first, flag);
   RET_LAST;
 }
 extern "C" int dbx_sumsq(const float* x, long long n, double* out, hipStream_t st) {

@@ -55,7 +55,7 @@ class NativeTrainer:
                  bucket_cap_mb: float = 64.0, allreduce_dtype: torch.dtype = torch.float32,
                  process_group=None, src_hw: Optional[Tuple[int, int]] = None, mean=None, std=None,
                  zero_stage: int = 0, cutmix_alpha: float = 0.0, seed: int = 0,
-                 engine: Optional[EngineConfig] = None):
+                 engine: Optional[EngineConfig] = None, grad_accum: int = 1):
         self.dev = device
         self.cfg = cfg = engine if engine is not None else EngineConfig.current()
         optim = optim or OptimConfig()
@@ -82,10 +82,20 @@ class NativeTrainer:
         n = self.prog.n_params
         self.mom = torch.zeros(n, device=device)
         self.mom2 = torch.zeros(n, device=device) if optim.name in ("adam", "adamw") else None
-        self.hyper = torch.zeros(4, device=device)      # lr, bc1, bc2 (device-side, graph-safe)
+        self.hyper = torch.zeros(4, device=device)      # lr, bc1, bc2, window-start flag (device-side, graph-safe)
         self._hyper_dev = DeviceHyper(self.hyper)
         self.clip_work = torch.zeros(4, device=device)
         self.step_count = 0
+        # gradient accumulation: k - 1 micro-steps (forward + backward, no collective, no update) add
+        # the flat gradient into ``acc``; the k-th call is the boundary step -- the usual step with
+        # ``acc`` folded into the gradient before anything consumes it. hyper[3] tells the (captured)
+        # accumulate kernel whether a micro-step opens a window (overwrite) or continues one (add).
+        self.k = int(grad_accum)
+        if self.k < 1:
+            raise ValueError("grad_accum must be >= 1")
+        self.micro = 0  # position inside the window: calls to step() since the last boundary
+        self.acc = torch.zeros(n, device=device) if self.k > 1 else None
+        self.micro_graphs: List[Optional[torch.cuda.CUDAGraph]] = []
         # debug mode synchronizes after every kernel, which graph capture forbids; per-phase
         # profiling (DBX_PROFILE=phases: hipEvent timers + roctx ranges) needs eager phases too
         self.phase_timer = PhaseTimer() if "phases" in os.environ.get("DBX_PROFILE", "").split(",") else None
@@ -196,6 +206,7 @@ class NativeTrainer:
             self.zero = SegmentedZero(self.prog, optim, self.seg_ranges, self.prog.bn_param_blocks(),
                                       stage=zero_stage, process_group=process_group, comm=self.ncomm,
                                       collectives=self.segmented)
+            self.zero.grad_div = self.k
             self.mom = self.zero.m  # shard-sized optimizer state only
             self.mom2 = self.zero.v
         self.lars = self._lars_segments() if optim.name == "lars" else None
@@ -264,6 +275,12 @@ class NativeTrainer:
             phases.append(("opt_norm", z.norm_phase, z.allreduce_norm))
         phases.append(("optimizer", self._optimizer_phase, z.gather if z is not None else None))
         self.phases = phases
+        # micro-step (grad_accum > 1): the same forward / backward phases without their collectives
+        # (DDP's no_sync), the optimizer phases replaced by one pass adding the gradient into ``acc``
+        self.micro_phases = None
+        if self.k > 1:
+            self.micro_phases = [(n, fn, None) for n, fn, _ in phases if n not in ("optimizer", "opt_norm")]
+            self.micro_phases.append(("accumulate", self._accumulate_phase, None))
 
     def _optimizer_ranges(self):
         """The optimizer inside the backward (engine field ``overlap_optimizer``): SGD / Adam are
@@ -276,6 +293,8 @@ class NativeTrainer:
         updated in the optimizer phase. Off (None) for clipping / LARS (global norms), ZeRO (its own
         sharded update), the c10d per-segment graphs and the batched side-stream layouts."""
         p, cfg = self.prog, self.cfg
+        if self.k > 1:  # (the accumulator is folded in at the top of the optimizer phase)
+            return None
         if not (cfg.overlap_optimizer != 0 and self.zero is None and self.lars is None
                 and not (self.opt.grad_clip and self.opt.grad_clip > 0)
                 and p.side_block and p.overlap_wgrad and (not self.segmented or self.block_posts)):
@@ -301,7 +320,7 @@ class NativeTrainer:
 
     def _update_range(self, lo: int, hi: int):
         p, o = self.prog, self.opt
-        gscale = 1.0 / (self.world * self.loopback)
+        gscale = 1.0 / (self.world * self.loopback * self.k)
         if o.name == "sgd":
             K.sgd_step(p.master[lo:hi], p.grad[lo:hi], self.mom[lo:hi], None, lr=o.lr, momentum=o.momentum,
                        dampening=o.dampening, weight_decay=o.weight_decay, nesterov=o.nesterov, first=False,
@@ -374,8 +393,18 @@ class NativeTrainer:
                               for r in rs], dtype=torch.int32, device=dev)
         return off, ln, adapt, torch.zeros(K.LARS_MAX_BLOCKS * 2 * len(rs), device=dev, dtype=torch.float64), max(r[2] for r in rs)
 
+    def _accumulate_phase(self):
+        K.grad_accum(self.acc, self.prog.grad, flag=self.hyper[3:4])
+
+    def _fold(self, lo: int, hi: int):
+        """Boundary step: grad[lo:hi] += acc[lo:hi] (on the current stream, before the range's consumer)."""
+        K.grad_accum(self.prog.grad[lo:hi], self.acc[lo:hi])
+
     def _optimizer_phase(self):
         p, o = self.prog, self.opt
+        if self.k > 1 and not self.segmented:
+            # no per-range collective folded the accumulator in: once over the whole buffer
+            self._fold(0, p.grad.numel())
         if self.zero is not None:
             # ZeRO-1/2: update this rank's shard of the fp32 master with its shard of the optimizer
             # state (the reduce-scatter and the all-gather run around this phase, not inside it:
@@ -390,7 +419,7 @@ class NativeTrainer:
                 self._update_range(*r)
             return
         gsp = None
-        gdiv = self.world * self.loopback  # the reduced gradient is a sum over gdiv replicas
+        gdiv = self.world * self.loopback * self.k  # the reduced gradient is a sum over gdiv micro-batches
         if o.grad_clip and o.grad_clip > 0:
             # clip on the averaged gradient: factor computed on device (no host sync)
             K.global_norm_clip_factor(p.grad, o.grad_clip * gdiv, self.clip_work)
@@ -426,8 +455,10 @@ class NativeTrainer:
             for rg in post:
                 self._post(rg)
         elif self.zero is not None:
-            self.zero.reduce_range(*post)
+            self.zero.reduce_range(*post, pre=self._fold if self.k > 1 else None)
         else:
+            if self.k > 1:  # the window's sum goes into the collective: fold right in front of it
+                self._fold(*post)
             self._allreduce_range(*post)
 
     def _allreduce_range(self, lo: int, hi: int):
@@ -481,15 +512,29 @@ class NativeTrainer:
         p.mix_box.copy_(box, non_blocking=True)
         p.mix_lam.copy_(lamt, non_blocking=True)
 
-    def _set_hyper(self):
+    def _set_hyper(self, boundary: bool = True):
         o = self.opt
-        self.step_count += 1
-        t = self.step_count
+        # optimizer steps, not micro-steps, are counted (Adam's bias corrections, zero.step_count); a
+        # micro-step carries the values of the update its window ends with
+        if boundary:
+            self.step_count += 1
+        t = self.step_count if boundary else self.step_count + 1
+        first = 1.0 if (self.k > 1 and self.micro == 0) else 0.0  # this micro-step opens a window
         if o.name in ("sgd", "lars"):
-            vals = [o.lr, 1.0, 1.0, 0.0]
+            vals = [o.lr, 1.0, 1.0, first]
         else:
-            vals = [o.lr, 1.0 - o.betas[0] ** t, 1.0 - o.betas[1] ** t, 0.0]
+            vals = [o.lr, 1.0 - o.betas[0] ** t, 1.0 - o.betas[1] ** t, first]
         self._hyper_dev.set(vals)
+
+    @property
+    def grad_accum(self) -> int:
+        """Micro-batches per optimizer step."""
+        return self.k
+
+    @property
+    def at_boundary(self) -> bool:
+        """True when the next ``step()`` applies the optimizer update (always, without accumulation)."""
+        return self.micro == self.k - 1
 
     def set_lr(self, lr: float):
         self.opt.lr = float(lr)
@@ -500,21 +545,25 @@ class NativeTrainer:
         # (inside the one-graph capture the comm stream joins only after its first fork: no wait on
         # work recorded outside the capture)
         first = i == 0 and not getattr(self, "_capturing_one", False)
-        return self.segmented and (first or name in ("optimizer", "opt_norm"))
+        # (the accumulate phase of a micro-step reads the whole gradient like the optimizer does)
+        return self.segmented and (first or name in ("optimizer", "opt_norm", "accumulate"))
 
-    def _run_phases_eager(self):
+    def _run_phases_eager(self, micro: bool = False):
+        phases = self.micro_phases if micro else self.phases
         if self.dev.type != "cuda":  # CPU (reference ops; gloo collectives, synchronous)
-            for i, (name, fn, post) in enumerate(self.phases):
+            for i, (name, fn, post) in enumerate(phases):
                 fn()
-                if self.segmented:
+                if self.segmented and post is not None:
                     self._post(post)
                 self._after_phase_updates(i)
             return
         cur = torch.cuda.current_stream(self.dev)
-        for i, (name, fn, post) in enumerate(self.phases):
+        for i, (name, fn, post) in enumerate(phases):
             if self._waits_comm(i, name):
                 self.prog.launch_pending()
-                cur.wait_stream(self.comm_stream)
+                # (a micro-step's one-graph capture forks no comm stream: nothing of it to wait for)
+                if not (micro and getattr(self, "_capturing_one", False)):
+                    cur.wait_stream(self.comm_stream)
             if self.phase_timer is not None:
                 with self.phase_timer.phase(name):
                     fn()
@@ -529,16 +578,21 @@ class NativeTrainer:
                         self._post(post)
             self._after_phase_updates(i)
 
-    def _graph_phases(self):
-        return self.phases
+    def _graph_phases(self, micro: bool = False):
+        return self.micro_phases if micro else self.phases
 
-    def _capture(self):
-        """Capture each phase (or the whole step when not segmented) into HIP graphs."""
+    def _capture(self, micro: bool = False):
+        """Capture each phase (or the whole step when not segmented) into HIP graphs: the full /
+        boundary step into ``graphs``, the micro-step of gradient accumulation into ``micro_graphs``."""
         release_dead_graphs(self.dev)
         s = torch.cuda.Stream(device=self.dev)
         s.wait_stream(torch.cuda.current_stream(self.dev))
         pool = torch.cuda.graph_pool_handle()
-        self.graphs = []
+        graphs: List[Optional[torch.cuda.CUDAGraph]] = []
+        if micro:
+            self.micro_graphs = graphs
+        else:
+            self.graphs = graphs
         # thread-local capture whenever a process group exists: its watchdog thread polls the
         # completion events of earlier collectives while we capture, and under the default
         # global mode such a query from another thread invalidates the capture
@@ -550,37 +604,39 @@ class NativeTrainer:
                 self._capturing_one = True
                 try:
                     with torch.cuda.graph(g, pool=pool, stream=s, capture_error_mode=mode):
-                        self._run_phases_eager()
+                        self._run_phases_eager(micro)
                         self.prog.launch_pending()
-                        torch.cuda.current_stream(self.dev).wait_stream(self.comm_stream)
+                        if not micro:
+                            torch.cuda.current_stream(self.dev).wait_stream(self.comm_stream)
                 finally:
                     self._capturing_one = False
-                self.graphs = [g]
+                graphs.append(g)
             elif not self.segmented:
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, pool=pool, stream=s, capture_error_mode=mode):
-                    for i, (_, fn, _) in enumerate(self.phases):
+                    for i, (_, fn, _) in enumerate(self._graph_phases(micro)):
                         fn()
                         self._after_phase_updates(i)
                     self.prog.launch_pending()
-                self.graphs = [g]
+                graphs.append(g)
             else:
-                for _, fn, _ in self._graph_phases():
+                for _, fn, _ in self._graph_phases(micro):
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, pool=pool, stream=s, capture_error_mode=mode):
                         fn()
-                    self.graphs.append(g)
+                    graphs.append(g)
         torch.cuda.current_stream(self.dev).wait_stream(s)
         torch.cuda.synchronize(self.dev)
 
-    def _replay(self):
+    def _replay(self, micro: bool = False):
         cur = torch.cuda.current_stream(self.dev)
+        graphs = self.micro_graphs if micro else self.graphs
         if not self.segmented or self.ncomm is not None:
             if self.ncomm is not None:
                 cur.wait_stream(self.comm_stream)  # eager warm-up collectives
-            self.graphs[0].replay()
+            graphs[0].replay()
             return
-        for i, ((name, _, post), g) in enumerate(zip(self._graph_phases(), self.graphs)):
+        for i, ((name, _, post), g) in enumerate(zip(self._graph_phases(micro), graphs)):
             if self._waits_comm(i, name):
                 cur.wait_stream(self.comm_stream)
             g.replay()
@@ -607,33 +663,36 @@ class NativeTrainer:
             p.flip.copy_(flips, non_blocking=True)
         if self.cutmix_alpha > 0:
             self._sample_cutmix()
-        self._set_hyper()
+        # gradient accumulation: every call but the window's last is a micro-step
+        boundary = self.micro == self.k - 1
+        self._set_hyper(boundary)
         try:
-            self._step_inner()
+            self._step_inner(micro=not boundary)
         except BaseException:
             p.drop_pending()  # a side batch deferred by the failed step must not launch later
             raise
+        self.micro = 0 if boundary else self.micro + 1
         if self.zero is not None:
             # a replayed graph does not run zero.step() in Python: keep its counter (saved in
             # ZeRO checkpoints) on the trainer's
             self.zero.step_count = self.step_count
 
-    def _step_inner(self):
+    def _step_inner(self, micro: bool = False):
         if not self.use_graphs:
-            self._run_phases_eager()
+            self._run_phases_eager(micro)
             return
-        if not self.graphs:
+        if not (self.micro_graphs if micro else self.graphs):
             # two eager warm-up steps (allocator / library handles), then capture. The warm-up
-            # steps are real steps: they update weights like any other.
-            if not hasattr(self, "_warm"):
-                self._warm = 0
-            if self._warm < 2:
-                self._warm += 1
-                self._run_phases_eager()
+            # steps are real steps: they update weights like any other. (Each step kind -- full /
+            # boundary, micro -- warms up and is captured on its own.)
+            warm = "_warm_micro" if micro else "_warm"
+            if getattr(self, warm, 0) < 2:
+                setattr(self, warm, getattr(self, warm, 0) + 1)
+                self._run_phases_eager(micro)
                 return
             # stream capture records without executing: no state to snapshot
-            self._capture()
-        self._replay()
+            self._capture(micro)
+        self._replay(micro)
 
     # ----------------------------------------------------------------------------------
     @torch.no_grad()

@@ -1343,6 +1343,19 @@ def adam_step(p, g, m, v, p16=None, *, lr, beta1, beta2, eps, weight_decay, deco
 
 
 @_dispatch
+def grad_accum(dst, src, *, first=False, flag=None):
+    """Gradient accumulation: dst = src when ``first`` else dst + src (flat fp32, any 4-byte aligned
+    slices). ``flag`` (fp32[1] device tensor) overrides ``first`` at run time (non-zero = first), so a
+    captured micro-step serves every window position; in first mode dst is not read."""
+    _chk(dst, torch.float32, "dst")
+    _chk(src, torch.float32, "src", dst.numel())
+    if flag is not None:
+        _chk(flag, torch.float32, "flag", 1)
+    C().grad_accum(dst.data_ptr(), src.data_ptr(), dst.numel(), int(bool(first)), _p(flag), stream_ptr())
+    return dst
+
+
+@_dispatch
 def global_norm_clip_factor(g, max_norm, work):
     """work: fp32[4] scratch (work[0:2] holds the fp64 sum of squares); returns work[2:4] =
     (factor, norm) on device (no host sync)."""

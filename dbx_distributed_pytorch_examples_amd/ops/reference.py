@@ -413,6 +413,20 @@ def adam_step(p, g, m, v, p16=None, *, lr, beta1, beta2, eps, weight_decay, deco
         p16.copy_(p.bfloat16())
 
 
+def grad_accum(dst, src, *, first=False, flag=None):
+    if dst.dtype != torch.float32 or src.dtype != torch.float32:
+        raise TypeError("grad_accum: expected float32 tensors")
+    if dst.numel() != src.numel() or not (dst.is_contiguous() and src.is_contiguous()):
+        raise ValueError("grad_accum: dst and src must be contiguous with equal numel")
+    if flag is not None:
+        first = float(flag.reshape(-1)[0]) != 0.0
+    if first:
+        dst.copy_(src.view_as(dst))  # (a copy: NaN / Inf left in dst must not survive)
+    else:
+        dst.add_(src.view_as(dst))
+    return dst
+
+
 def global_norm_clip_factor(g, max_norm, work):
     work.zero_()
     ss = (g.double() ** 2).sum()

@@ -238,6 +238,9 @@ class SegmentedZero:
         self.param16 = prog.param16
         self.work = torch.zeros(4, device=dev)  # [0:2] fp64 sum of squares, [2] clip factor, [3] norm
         self.step_count = 0
+        # extra divisor of the reduced gradient next to the world size (the native trainer's gradient
+        # accumulation: the gradient is then a sum over world x grad_div micro-batches)
+        self.grad_div = 1
         # exact fp32 exchange of the BN affine blocks: this rank's pieces summed with zeros elsewhere
         self.bn_ranges = [tuple(b) for b in bn_ranges]
         nbn = sum(hi - lo for lo, hi in self.bn_ranges)
@@ -297,13 +300,17 @@ class SegmentedZero:
         K.cast_f32_bf16(self.prog.master, self.param16)
 
     # ---- collectives (issued between graph replays, on the comm stream) -------------------
-    def reduce_range(self, lo: int, hi: int) -> None:
-        """Reduce-scatter every part inside the backward range [lo, hi)."""
+    def reduce_range(self, lo: int, hi: int, pre=None) -> None:
+        """Reduce-scatter every part inside the backward range [lo, hi). ``pre(plo, phi)``: issued
+        right in front of each part's collective on the same stream (the trainer folds its gradient
+        accumulator into the part there)."""
         if not self.coll:
             return
         for part in self.parts:
             plo, phi, per, own, so = part
             if lo <= plo < hi:
+                if pre is not None:
+                    pre(plo, phi)
                 self._rs(self.gsh[so:so + per], self.prog.grad[plo:phi])
 
     def allreduce_norm(self) -> None:
@@ -349,7 +356,7 @@ class SegmentedZero:
         """Shard update (fused kernels), writing the bf16 shard for the all-gather (world 1: the
         full bf16 copy directly). Clipping: ``norm_phase`` (+ ``allreduce_norm``) ran before."""
         from ..ops import kernels as K
-        o, W = self.o, self.world
+        o, W = self.o, self.world * self.grad_div
         gs = 1.0 / W
         gsp = None
         if getattr(o, "grad_clip", 0.0):

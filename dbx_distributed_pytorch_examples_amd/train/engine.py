@@ -138,7 +138,8 @@ class _Native:
                                     label_smoothing=cfg.data.label_smoothing, use_graphs=cfg.graphs,
                                     bucket_cap_mb=cfg.bucket_cap_mb, allreduce_dtype=ar,
                                     src_hw=(h, w), mean=mean, std=std, zero_stage=cfg.zero.stage,
-                                    cutmix_alpha=cfg.data.cutmix_alpha, seed=cfg.seed)
+                                    cutmix_alpha=cfg.data.cutmix_alpha, seed=cfg.seed,
+                                    grad_accum=cfg.grad_accum)
         if not cfg.data.augment:
             aug = AugmentSpec()
         elif (h, w) == (s, s) and s <= 64:
@@ -272,7 +273,9 @@ def _pick_engine(cfg: TrainConfig, model, ds, dev) -> str:
     frozen = isinstance(model, FrozenBackboneClassifier) and supports(model.resnet) and \
         not any(p.requires_grad for p in model.resnet.parameters() if p is not None and
                 not any(p is q for q in model.resnet.fc.parameters()))
-    if dev.type == "cuda" and (supports(model) or frozen) and _uint8_source(ds) and cfg.grad_accum == 1 \
+    # (gradient accumulation: the native trainer's micro-steps; the frozen-backbone trainer has none)
+    if dev.type == "cuda" and (supports(model) or frozen) and _uint8_source(ds) \
+            and (cfg.grad_accum == 1 or not frozen) \
             and (cfg.data.cutmix_alpha == 0 or not frozen):  # CutMix: native box paste + soft-target CE
         return "native"
     return "autograd"
@@ -355,6 +358,10 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
                                "scheduler": cfg.sched.name, "num_gpus": ddist.get_world_size(), "engine": engine,
                                "zero_stage": cfg.zero.stage, "trainer": "dbx_amd"})
         _log(f"[train] engine={engine} world={ddist.get_world_size()} steps/epoch={spe} total_steps={total}")
+        if cfg.grad_accum > 1 and cfg.checkpoint_dir and cfg.checkpoint_every and spe % cfg.grad_accum != 0:
+            # (one iteration is one micro-batch; a checkpoint carries no accumulator)
+            _log(f"[train] warning: steps/epoch={spe} is no multiple of grad_accum={cfg.grad_accum}: a run resumed "
+                 "from an epoch checkpoint drops the micro-batches of the window that was open at that epoch's end")
         best_val, bad_epochs = -1.0, 0
         t_start = time.perf_counter()
         imgs = 0
@@ -525,5 +532,7 @@ def _restore_trainer_state(runner, st):
         if "mom2" in st and tr.mom2 is not None:
             tr.mom2.copy_(st["mom2"])
         tr.step_count = int(st.get("step_count", 0))
+        if hasattr(tr, "micro"):
+            tr.micro = 0  # no accumulator is saved: a partial window is dropped, the next call opens one
     elif st.get("kind") == "torch" and getattr(tr, "opt", None) is not None:
         tr.opt.load_state_dict(st["optimizer"])
