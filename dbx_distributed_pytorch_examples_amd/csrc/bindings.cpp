@@ -76,7 +76,6 @@ int dbx_colsum(const bf16*, float*, int, int, int, hipStream_t);
 int dbx_dropout(const bf16*, bf16*, long long, unsigned long long, unsigned, unsigned, float, const unsigned*,
                 hipStream_t);
 int dbx_cast_f32_bf16(const float*, bf16*, long long, hipStream_t);
-int dbx_cast_bf16_f32(const bf16*, float*, long long, float, int, hipStream_t);
 }
 
 template <typename T>
@@ -381,9 +380,6 @@ PYBIND11_MODULE(_C, m) {
   });
   m.def("cast_f32_bf16", [](uintptr_t x, uintptr_t y, long long n, uintptr_t st) {
     check(dbx_cast_f32_bf16(P<const float*>(x), P<bf16*>(y), n, S(st)), "cast_f32_bf16");
-  });
-  m.def("cast_bf16_f32", [](uintptr_t x, uintptr_t y, long long n, float scale, int acc, uintptr_t st) {
-    check(dbx_cast_bf16_f32(P<const bf16*>(x), P<float*>(y), n, scale, acc, S(st)), "cast_bf16_f32");
   });
   m.attr("arch") = "gfx950";
 }

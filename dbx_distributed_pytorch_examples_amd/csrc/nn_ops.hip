@@ -1062,10 +1062,6 @@ __global__ __launch_bounds__(256) void weight_prep_kernel(const T* __restrict__ 
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ x, bf16* __restrict__ y, long long n) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) y[i] = (bf16)x[i];
 }
-__global__ void cast_bf16_f32_kernel(const bf16* __restrict__ x, float* __restrict__ y, long long n, float scale, int accumulate) {
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    y[i] = (accumulate ? y[i] : 0.f) + scale * (float)x[i];
-}
 
 }  // namespace dbx
 
@@ -1284,9 +1280,5 @@ extern "C" int dbx_weight_prep16(const bf16* src, bf16* wbuf, const void* desc_d
 }
 extern "C" int dbx_cast_f32_bf16(const float* x, bf16* y, long long n, hipStream_t st) {
   hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, y, n);
-  RET_LAST;
-}
-extern "C" int dbx_cast_bf16_f32(const bf16* x, float* y, long long n, float scale, int accumulate, hipStream_t st) {
-  hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, y, n, scale, accumulate);
   RET_LAST;
 }

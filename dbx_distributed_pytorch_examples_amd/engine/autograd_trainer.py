@@ -56,7 +56,8 @@ def build_torch_optimizer(params, o):
         return LARS(params, lr=o.lr, momentum=o.momentum, weight_decay=o.weight_decay,
                     trust_coefficient=getattr(o, "trust_coefficient", 0.001), nesterov=o.nesterov)
     if o.name == "sgd":
-        return torch.optim.SGD(params, lr=o.lr, momentum=o.momentum, nesterov=o.nesterov, weight_decay=o.weight_decay)
+        return torch.optim.SGD(params, lr=o.lr, momentum=o.momentum, dampening=getattr(o, "dampening", 0.0),
+                               nesterov=o.nesterov, weight_decay=o.weight_decay)
     if o.name == "adam":
         return torch.optim.Adam(params, lr=o.lr, betas=tuple(o.betas), eps=o.eps, weight_decay=o.weight_decay)
     if o.name == "adamw":

@@ -62,6 +62,7 @@ class NativeHead:
                  label_smoothing: float = 0.0, seed: int = 0):
         from ..ops import kernels as K
         self.K = K
+        K.reject_dampening(optim)
         lins = [m for m in head.modules() if isinstance(m, nn.Linear)]
         if len(lins) != 1 or any(not isinstance(m, (nn.Linear, nn.Dropout, nn.Sequential, nn.Identity))
                                  for m in head.modules()):

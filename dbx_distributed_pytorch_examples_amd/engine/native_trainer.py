@@ -59,6 +59,7 @@ class NativeTrainer:
         self.dev = device
         self.cfg = cfg = engine if engine is not None else EngineConfig.current()
         optim = optim or OptimConfig()
+        K.reject_dampening(optim)
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         if zero_stage and optim.name == "lars":

@@ -650,12 +650,7 @@ class ResNetProgram:
         self.mix_perm = self.mix_box = self.mix_lam = self.labels2 = None
 
     def _pack_wdesc(self, descs) -> torch.Tensor:
-        # WDesc {long long src, fwd, tr; int K, RS, C, pad} = 40 bytes
-        raw = []
-        for (src, f, t, k, rs, c) in descs:
-            raw.append(torch.tensor([src, f, t], dtype=torch.int64).view(torch.int32))
-            raw.append(torch.tensor([k, rs, c, 0], dtype=torch.int32))
-        return torch.cat(raw).to(self.dev)
+        return K.pack_wdesc(descs, self.dev)
 
     def _pack_step_descs(self) -> None:
         """The training step's weight-prep launch also zeroes the BN statistics slabs and counts

@@ -53,6 +53,8 @@ def _dispatch(fn):
     def wrapper(*args, **kw):
         global _POST_LAUNCH
         t = args[0]
+        if not isinstance(t, torch.Tensor):  # (an optional first argument left out: bn_eval_coeff's gamma)
+            t = next((a for a in args if isinstance(a, torch.Tensor)), None)
         if isinstance(t, torch.Tensor) and not use_native(t):
             return ref(*args, **kw)
         r = checked(*args, **kw) if _debug.enabled() else fn(*args, **kw)
@@ -983,6 +985,7 @@ def bn_eval_coeff(gamma, beta, eps, running_mean, running_var, scale, shift):
 @_dispatch
 def channel_stats(y, stats):
     Cc = y.shape[-1]
+    _ref.check_channels(Cc)
     _chk(y, torch.bfloat16, "y")
     nsh = _chk_stats(stats, "stats", Cc)
     C().channel_stats(y.data_ptr(), y.numel() // Cc, Cc, stats.data_ptr(), nsh, stream_ptr())
@@ -997,6 +1000,7 @@ def bn_apply(y, scale, shift, out, *, res=None, res_scale=None, res_shift=None, 
     (res_scale / res_shift) is done inside this launch (the bn_finalize launch it replaces, bit for bit;
     its outputs are stored on the way)."""
     Cc = y.shape[-1]
+    _ref.check_channels(Cc)
     _chk(y, torch.bfloat16, "y")
     _chk(out, torch.bfloat16, "out", y.numel())
     mode = 0
@@ -1022,6 +1026,7 @@ def bn_apply(y, scale, shift, out, *, res=None, res_scale=None, res_shift=None, 
 @_dispatch
 def bn_bwd_reduce(dout, y, mean, invstd, stats, *, mask_mode, mref=None, scale=None, shift=None):
     Cc = y.shape[-1]
+    _ref.check_channels(Cc)
     _chk(dout, torch.bfloat16, "dout", y.numel())
     _chk(y, torch.bfloat16, "y")
     nsh = _chk_stats(stats, "stats", Cc)
@@ -1044,6 +1049,7 @@ def bn_bwd_apply(dout, y, coeff, dy, *, mask_mode, mref=None, scale=None, shift=
     the coefficients are finalized inside this launch from the BN's moment shards (the bn_bwd_coeff
     launch it replaces, bit for bit; ``coeff`` / dgamma / dbeta are stored on the way)."""
     Cc = y.shape[-1]
+    _ref.check_channels(Cc)
     _chk(dy, torch.bfloat16, "dy", y.numel())
     if gout is not None:
         _chk(gout, torch.bfloat16, "gout", y.numel())
@@ -1060,6 +1066,7 @@ def bn_bwd_apply2(g, y1, coeff1, dy1, y2, coeff2, dy2, fin1=None, fin2=None):
     dy1 = k1*g + k2*y1 + k3 (coeff1), dy2 likewise with y2 / coeff2; ``fin1`` / ``fin2`` as in
     :func:`bn_bwd_apply`."""
     Cc = y1.shape[-1]
+    _ref.check_channels(Cc)
     for t, nm in ((g, "g"), (y1, "y1"), (dy1, "dy1"), (y2, "y2"), (dy2, "dy2")):
         _chk(t, torch.bfloat16, nm, y1.numel())
     _chk(coeff1, torch.float32, "coeff1", 3 * Cc)
@@ -1081,6 +1088,7 @@ def maxpool_fwd(x, out, arg, *, K=3, stride=2, pad=1, scale=None, shift=None, re
     ``fin`` (:class:`BnFin`, mode FWD): the stem BN's forward finalize, done inside this launch."""
     N, H, W, Cc = x.shape
     _, P, Q, _ = out.shape
+    _ref.check_channels(Cc)
     _chk(x, torch.bfloat16, "x")
     _chk(out, torch.bfloat16, "out")
     _chk(arg, torch.uint8, "arg", out.numel())
@@ -1308,6 +1316,15 @@ def sgd_step(p, g, v, p16=None, *, lr, momentum, dampening=0.0, weight_decay=0.0
             float(weight_decay), int(nesterov), int(first), _p(grad_scale_ptr), float(grad_scale), stream_ptr())
 
 
+def reject_dampening(optim) -> None:
+    """The trainers run :func:`sgd_step` with ``first=False`` on a zeroed momentum buffer (a captured step
+    cannot tell its first replay from the others), which equals torch's first-step rule ``buf = d`` only
+    without dampening: refuse a configuration that would silently train differently from torch.optim.SGD."""
+    if float(getattr(optim, "dampening", 0.0) or 0.0) != 0.0:
+        raise ValueError("SGD dampening is not supported by the trainers (momentum buffers start at zero, so "
+                         "the first step would be damped, unlike torch.optim.SGD); use dampening=0")
+
+
 LARS_MAX_BLOCKS = 64  # csrc/nn_ops.hip kLarsMaxBlocks
 
 
@@ -1412,6 +1429,22 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None):
     C().augment_u8(img.data_ptr(), out.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Cin, Ho, Wo,
                    float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]), float(std[2]),
                    _p(perm), _p(mixbox), stream_ptr())
+
+
+def pack_wdesc(descs, device) -> torch.Tensor:
+    """Descriptor table of one :func:`weight_prep` launch (csrc/nn_ops.hip WDesc {int64 src, fwd, tr;
+    int32 K, RS, C, pad} = 40 bytes per entry) from ``(src, fwd, tr, K, RS, C)`` tuples. ``tr >= 0``: a
+    conv weight with a transposed (CRSK) dgrad copy at element offset ``tr``; -1: plain cast; -2: the stem
+    (RS = R * 16 + S); -3 / -4: zero K doubles / add 1 to K int64 counters at the address ``src``. The
+    transposed copy is made in 64 x 64 (k, c) tiles: other channel counts would be truncated, so they
+    are refused here."""
+    raw = []
+    for (src, f, t, k, rs, c) in descs:
+        if t >= 0 and (k <= 0 or c <= 0 or k % 64 or c % 64):
+            raise ValueError(f"weight_prep: a transposed entry needs K and C multiples of 64, got K={k}, C={c}")
+        raw.append(torch.tensor([src, f, t], dtype=torch.int64).view(torch.int32))
+        raw.append(torch.tensor([k, rs, c, 0], dtype=torch.int32))
+    return torch.cat(raw).to(device)
 
 
 @_dispatch

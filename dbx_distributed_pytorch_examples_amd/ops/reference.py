@@ -17,6 +17,20 @@ NSHARD = 32  # BN-statistics shards of the large steps (see kernels.NSHARD; smal
 MASK_NONE, MASK_OUT, MASK_Y = 0, 1, 2
 
 
+def check_channels(C: int) -> None:
+    """The per-channel passes give a thread one 8-channel group of a row, at most 256 groups a row."""
+    if C < 8 or C % 8 or C // 8 > 256:
+        raise ValueError(f"per-channel kernels need a channel count that is a multiple of 8, at most 2048; got {C}")
+
+
+def _shards(stats, C: int):
+    """The statistics slab as [nshard, 2, C] (at most 32 shards, as the kernels read it)."""
+    n = stats.numel() // (2 * C)
+    if n < 1 or n > 32 or n * 2 * C != stats.numel():
+        raise ValueError(f"statistics slab of {stats.numel()} elements is not [nshard <= 32, 2, {C}]")
+    return stats.view(n, 2, C)
+
+
 def _nchw(x):
     return x.permute(0, 3, 1, 2)
 
@@ -161,7 +175,7 @@ def conv_dwfused(g, y3, coeff, wt16, y2, scale2, shift2, mean2, invstd2, bstats2
 def bn_finalize(stats, count, gamma, beta, eps, momentum, running_mean, running_var, scale, shift, save_mean,
                 save_invstd):
     C = scale.numel()
-    st = stats.view(-1, 2, C).double().sum(0)
+    st = _shards(stats, C).double().sum(0)
     mean = st[0] / count
     var = (st[1] / count - mean * mean).clamp_min(0)
     invstd = 1.0 / torch.sqrt(var + eps)
@@ -188,6 +202,7 @@ def bn_eval_coeff(gamma, beta, eps, running_mean, running_var, scale, shift):
 
 
 def channel_stats(y, stats):
+    check_channels(y.shape[-1])
     _add_stats(stats, y)
 
 
@@ -196,6 +211,7 @@ def bn_apply(y, scale, shift, out, *, res=None, res_scale=None, res_shift=None, 
     for fn in (fin, res_fin):  # (the kernel finalizes in-launch; here: the finalize first)
         if fn is not None:
             fn.run()
+    check_channels(y.shape[-1])
     f = y.float() * scale + shift
     if res is not None:
         r = res.float()
@@ -225,6 +241,7 @@ def _g(dout, y, mask_mode, mref, scale, shift):
 
 def bn_bwd_reduce(dout, y, mean, invstd, stats, *, mask_mode, mref=None, scale=None, shift=None):
     C = y.shape[-1]
+    check_channels(C)
     g = _g(dout, y, mask_mode, mref, scale, shift).reshape(-1, C)
     xhat = ((y.float() - mean) * invstd).reshape(-1, C)
     st = stats.view(-1, 2, C)
@@ -234,7 +251,7 @@ def bn_bwd_reduce(dout, y, mean, invstd, stats, *, mask_mode, mref=None, scale=N
 
 def bn_bwd_coeff(stats, count, gamma, mean, invstd, coeff, dgamma=None, dbeta=None, accumulate=False):
     C = mean.numel()
-    st = stats.view(-1, 2, C).sum(0).float()
+    st = _shards(stats, C).sum(0).float()
     s, q = st[0], st[1]
     g = gamma if gamma is not None else torch.ones_like(mean)
     sg, sgx = s / count, q / count
@@ -252,6 +269,7 @@ def bn_bwd_apply(dout, y, coeff, dy, *, mask_mode, mref=None, scale=None, shift=
     if fin is not None:  # (the kernel finalizes the coefficients in-launch; here: the finalize first)
         fin.run()
     C = y.shape[-1]
+    check_channels(C)
     g = _g(dout, y, mask_mode, mref, scale, shift)
     if gout is not None:
         gout.copy_(g.bfloat16())
@@ -267,6 +285,7 @@ def bn_bwd_apply2(g, y1, coeff1, dy1, y2, coeff2, dy2, fin1=None, fin2=None):
 def maxpool_fwd(x, out, arg, *, K=3, stride=2, pad=1, scale=None, shift=None, relu=True, ymax=None, fin=None):
     if fin is not None:
         fin.run()
+    check_channels(x.shape[-1])
     f = x.float()
     if scale is not None:
         f = f * scale + shift

@@ -215,6 +215,7 @@ class ShardedDataParallel(nn.Module):
         self.prefetch_elems = int(prefetch_elems)
         if optim.name not in ("sgd", "adam", "adamw"):
             raise ValueError(f"ZeRO-3 supports sgd / adam / adamw, not {optim.name!r}")
+        K.reject_dampening(optim)
         self.module = module
         self.o = optim
         self.pg = process_group

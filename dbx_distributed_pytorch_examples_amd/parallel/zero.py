@@ -65,6 +65,7 @@ class ZeroShardedOptimizer:
             raise ValueError("ZeRO stage must be 1, 2 or 3")
         if optim.name not in ("sgd", "adam", "adamw"):
             raise ValueError(f"sharded optimizer supports sgd / adam / adamw, not {optim.name!r}")
+        K.reject_dampening(optim)
         if stage == 3:
             warnings.warn("flat-buffer ZeRO: stage 3 runs as stage 2 here; parameter sharding is parallel.fsdp.ShardedDataParallel")
             stage = 2
@@ -198,6 +199,7 @@ class SegmentedZero:
         rehearsal, where every collective is an identity but runs through RCCL)."""
         if optim.name not in ("sgd", "adam", "adamw"):
             raise ValueError(f"sharded optimizer supports sgd / adam / adamw, not {optim.name!r}")
+        K.reject_dampening(optim)
         if stage == 3:
             warnings.warn("native program: ZeRO stage 3 runs as stage 2 (the captured graph needs resident "
                           "parameters; parameter sharding is parallel.fsdp.ShardedDataParallel)")
