@@ -118,6 +118,9 @@ class TrainConfig:
     num_classes: int = 1000
     batch_size: int = 256              # per GPU (micro batch)
     grad_accum: int = 1
+    ema_decay: float = 0.0             # weight EMA (native engine): 0 = off, else the decay d in [0, 1)
+    ema_warmup: bool = False           # d_t = min(ema_decay, (1 + t) / (10 + t)) at optimizer step t
+    ema_eval: bool = True              # val_* metrics from the averaged weights when ema_decay > 0
     epochs: int = 1
     max_steps: int = 0                 # 0 = full epochs
     duration: str = ""                 # composer style: "2ep" / "100ba"

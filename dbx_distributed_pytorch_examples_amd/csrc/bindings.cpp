@@ -57,6 +57,12 @@ int dbx_sgd(float*, const float*, float*, bf16*, long long, const float*, float,
 int dbx_adam(float*, const float*, float*, float*, bf16*, long long, const float*, float, float, float, float, float, int,
              float, float, const float*, float, hipStream_t);
 int dbx_grad_accum(float*, const float*, long long, int, const float*, hipStream_t);
+int dbx_sgd_ema(float*, const float*, float*, bf16*, long long, const float*, float, float, float, float, int, int,
+                const float*, float, float*, const float*, float, hipStream_t);
+int dbx_adam_ema(float*, const float*, float*, float*, bf16*, long long, const float*, float, float, float, float, float,
+                 int, float, float, const float*, float, float*, const float*, float, hipStream_t);
+int dbx_ema_update(float*, const float*, long long, const float*, float, hipStream_t);
+int dbx_ema_update_multi(const void*, int, long long, const float*, float, hipStream_t);
 int dbx_sumsq(const float*, long long, double*, hipStream_t);
 int dbx_lars_scale(const float*, float*, const int*, const int*, const int*, int, int, double*, float, float, float,
                    hipStream_t);
@@ -313,6 +319,30 @@ PYBIND11_MODULE(_C, m) {
     check(dbx_lars_scale(P<const float*>(p), P<float*>(g), P<const int*>(off), P<const int*>(len),
                          P<const int*>(adapt), nseg, max_len, P<double*>(norms), gs, eta, wd, S(st)),
           "lars_scale");
+  });
+  m.def("sgd_ema", [](uintptr_t p, uintptr_t g, uintptr_t v, uintptr_t p16, long long n, uintptr_t hyper, float lr,
+                      float mom, float damp, float wd, int nesterov, int first, uintptr_t gsp, float gs, uintptr_t ema,
+                      uintptr_t omd_ptr, float omd, uintptr_t st) {
+    check(dbx_sgd_ema(P<float*>(p), P<const float*>(g), P<float*>(v), P<bf16*>(p16), n, P<const float*>(hyper), lr, mom,
+                      damp, wd, nesterov, first, P<const float*>(gsp), gs, P<float*>(ema), P<const float*>(omd_ptr),
+                      omd, S(st)),
+          "sgd_ema");
+  });
+  m.def("adam_ema", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t p16, long long n, uintptr_t hyper,
+                       float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2,
+                       uintptr_t gsp, float gs, uintptr_t ema, uintptr_t omd_ptr, float omd, uintptr_t st) {
+    check(dbx_adam_ema(P<float*>(p), P<const float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(p16), n,
+                       P<const float*>(hyper), lr, b1, b2, eps, wd, decoupled, bc1, bc2, P<const float*>(gsp), gs,
+                       P<float*>(ema), P<const float*>(omd_ptr), omd, S(st)),
+          "adam_ema");
+  });
+  m.def("ema_update", [](uintptr_t e, uintptr_t p, long long n, uintptr_t omd_ptr, float omd, uintptr_t st) {
+    check(dbx_ema_update(P<float*>(e), P<const float*>(p), n, P<const float*>(omd_ptr), omd, S(st)), "ema_update");
+  });
+  m.def("ema_update_multi", [](uintptr_t desc, int ntensors, long long max_len, uintptr_t omd_ptr, float omd,
+                               uintptr_t st) {
+    check(dbx_ema_update_multi(P<const void*>(desc), ntensors, max_len, P<const float*>(omd_ptr), omd, S(st)),
+          "ema_update_multi");
   });
   m.def("grad_accum", [](uintptr_t dst, uintptr_t src, long long n, int first, uintptr_t flag, uintptr_t st) {
     check(dbx_grad_accum(P<float*>(dst), P<const float*>(src), n, first, P<const float*>(flag), S(st)), "grad_accum");

@@ -714,13 +714,29 @@ __global__ void softmax_ce_kernel(const T* __restrict__ logits, const long long*
 //   Adam/AdamW: m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr * mhat/(sqrt(vhat)+eps)
 //   grad_scale multiplies g first (DDP averaging / loss scaling / clipping factor), read
 //   from device memory so it can be produced by a previous kernel (global-norm clip).
+//   Weight EMA (compile-time variant EMA = true): e = fmaf(omd, p_new - e, e) from the parameter about
+//   to be stored; omd = fl32(1 - decay), rounded once on the host (never 1 - d in fp32 here), read
+//   from omd_ptr (device fp32[1], nullable) when given so a captured step follows a decay schedule.
+//   Every EMA site goes through ema_lerp: fused and standalone updates give the same bits.
 // ----------------------------------------------------------------------------------------
+__device__ __forceinline__ float ema_lerp(float e, float p, float omd) { return fmaf(omd, p - e, e); }
+// the EMA variant's extra kernel arguments; empty for the plain instantiation (same code as without)
+template <bool EMA> struct EmaArgs { float* e; const float* omd_ptr; float omd; };
+template <> struct EmaArgs<false> {};
+
+template <bool EMA>
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v,
                            bf16* __restrict__ p16, long long n, const float* __restrict__ hyper, float lr, float mom,
                            float damp, float wd, int nesterov, int first, const float* __restrict__ gscale_ptr,
-                           float gscale) {
+                           float gscale, EmaArgs<EMA> ea) {
   // hyper (device, nullable): [lr] so a captured graph follows the LR schedule on replay
   if (hyper) lr = hyper[0];
+  [[maybe_unused]] float* __restrict__ ema = nullptr;
+  [[maybe_unused]] float omd = 0.f;
+  if constexpr (EMA) {
+    ema = ea.e;
+    omd = ea.omd_ptr ? ea.omd_ptr[0] : ea.omd;
+  }
   const float gs = gscale_ptr ? gscale * gscale_ptr[0] : gscale;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i * 4 < n; i += (long long)gridDim.x * blockDim.x) {
     const long long e = i * 4;
@@ -740,6 +756,12 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
         bf16x4 b = {(bf16)pp[0], (bf16)pp[1], (bf16)pp[2], (bf16)pp[3]};
         *reinterpret_cast<bf16x4*>(p16 + e) = b;
       }
+      if constexpr (EMA) {
+        f32x4 ee = *reinterpret_cast<f32x4*>(ema + e);
+        ee = f32x4{ema_lerp(ee[0], pp[0], omd), ema_lerp(ee[1], pp[1], omd), ema_lerp(ee[2], pp[2], omd),
+                   ema_lerp(ee[3], pp[3], omd)};
+        *reinterpret_cast<f32x4*>(ema + e) = ee;
+      }
     } else {
       for (long long k = e; k < n; ++k) {
         float gg = g[k] * gs + wd * p[k];
@@ -751,6 +773,7 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
         }
         p[k] -= lr * d;
         if (p16) p16[k] = (bf16)p[k];
+        if constexpr (EMA) ema[k] = ema_lerp(ema[k], p[k], omd);
       }
     }
   }
@@ -815,12 +838,19 @@ __global__ void lars_apply_kernel(const float* __restrict__ p, float* __restrict
     g[off + i] = scale * g[off + i] + decay * p[off + i];
 }
 
+template <bool EMA>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, bf16* __restrict__ p16, long long n, const float* __restrict__ hyper,
                             float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2,
-                            const float* __restrict__ gscale_ptr, float gscale) {
+                            const float* __restrict__ gscale_ptr, float gscale, EmaArgs<EMA> ea) {
   // hyper (device, nullable): [lr, 1-b1^t, 1-b2^t] so graph replays track the step count
   if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2 = hyper[2]; }
+  [[maybe_unused]] float* __restrict__ ema = nullptr;
+  [[maybe_unused]] float omd = 0.f;
+  if constexpr (EMA) {
+    ema = ea.e;
+    omd = ea.omd_ptr ? ea.omd_ptr[0] : ea.omd;
+  }
   const float gs = gscale_ptr ? gscale * gscale_ptr[0] : gscale;
   for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
     float gg = g[k] * gs;
@@ -833,6 +863,7 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
     pp -= lr * (mm / bc1) / (sqrtf(vv / bc2) + eps);
     p[k] = pp;
     if (p16) p16[k] = (bf16)pp;
+    if constexpr (EMA) ema[k] = ema_lerp(ema[k], pp, omd);
   }
 }
 
@@ -854,6 +885,36 @@ __global__ void grad_accum_kernel(float* __restrict__ dst, const float* __restri
     *reinterpret_cast<f32x4*>(dst + i * 4) = s;
   }
   for (long long k = n4 * 4 + tid; k < n; k += nth) dst[k] = first ? src[k] : dst[k] + src[k];
+}
+
+// Standalone weight EMA, e = ema_lerp(e, p, omd), for what no optimizer kernel touches. One kernel,
+// two launch shapes: desc == nullptr -- the flat slices (e, p, n), grid (blocks); desc != nullptr -- a
+// device table of {dst address, src address, length} entries, grid (blocks, ntensors) with blockIdx.y
+// the entry (the BatchNorm running statistics: separate module buffers, one launch for all of them).
+// Alignment policy of grad_accum_kernel, per entry: 16 B per lane when both pointers are 16-byte
+// aligned, scalar otherwise and for the n % 4 tail.
+struct EmaDesc { long long dst, src, len; };
+__global__ void ema_kernel(const EmaDesc* __restrict__ desc, float* __restrict__ e, const float* __restrict__ p,
+                           long long n, const float* __restrict__ omd_ptr, float omd) {
+  if (desc) {
+    const EmaDesc d = desc[blockIdx.y];
+    e = reinterpret_cast<float*>(d.dst);
+    p = reinterpret_cast<const float*>(d.src);
+    n = d.len;
+  }
+  if (omd_ptr) omd = omd_ptr[0];
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long nth = (long long)gridDim.x * blockDim.x;
+  const bool vec = ((reinterpret_cast<uintptr_t>(e) | reinterpret_cast<uintptr_t>(p)) & 15) == 0;
+  const long long n4 = vec ? n / 4 : 0;
+  for (long long i = tid; i < n4; i += nth) {
+    const f32x4 pp = *reinterpret_cast<const f32x4*>(p + i * 4);
+    f32x4 ee = *reinterpret_cast<const f32x4*>(e + i * 4);
+    ee = f32x4{ema_lerp(ee[0], pp[0], omd), ema_lerp(ee[1], pp[1], omd), ema_lerp(ee[2], pp[2], omd),
+               ema_lerp(ee[3], pp[3], omd)};
+    *reinterpret_cast<f32x4*>(e + i * 4) = ee;
+  }
+  for (long long k = n4 * 4 + tid; k < n; k += nth) e[k] = ema_lerp(e[k], p[k], omd);
 }
 
 // sum of squares over a flat fp32 buffer (global-norm clipping), one fp64 atomic per block. fp64
@@ -1220,15 +1281,47 @@ extern "C" int dbx_softmax_ce(const void* logits, int is_bf16, const long long* 
 extern "C" int dbx_sgd(float* p, const float* g, float* v, bf16* p16, long long n, const float* hyper, float lr,
                        float mom, float damp, float wd, int nesterov, int first, const float* gscale_ptr, float gscale,
                        hipStream_t st) {
-  hipLaunchKernelGGL(sgd_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, v, p16, n, hyper, lr, mom, damp,
-                     wd, nesterov, first, gscale_ptr, gscale);
+  hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, v, p16, n, hyper, lr, mom,
+                     damp, wd, nesterov, first, gscale_ptr, gscale, EmaArgs<false>{});
   RET_LAST;
 }
 extern "C" int dbx_adam(float* p, const float* g, float* m, float* v, bf16* p16, long long n, const float* hyper,
                         float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2,
                         const float* gscale_ptr, float gscale, hipStream_t st) {
-  hipLaunchKernelGGL(adam_kernel, dim3(grid_for(n)), dim3(256), 0, st, p, g, m, v, p16, n, hyper, lr, b1, b2, eps, wd,
-                     decoupled, bc1, bc2, gscale_ptr, gscale);
+  hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_for(n)), dim3(256), 0, st, p, g, m, v, p16, n, hyper, lr, b1, b2, eps,
+                     wd, decoupled, bc1, bc2, gscale_ptr, gscale, EmaArgs<false>{});
+  RET_LAST;
+}
+extern "C" int dbx_sgd_ema(float* p, const float* g, float* v, bf16* p16, long long n, const float* hyper, float lr,
+                           float mom, float damp, float wd, int nesterov, int first, const float* gscale_ptr,
+                           float gscale, float* ema, const float* omd_ptr, float omd, hipStream_t st) {
+  if (!ema) return -1;
+  hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, v, p16, n, hyper, lr, mom,
+                     damp, wd, nesterov, first, gscale_ptr, gscale, EmaArgs<true>{ema, omd_ptr, omd});
+  RET_LAST;
+}
+extern "C" int dbx_adam_ema(float* p, const float* g, float* m, float* v, bf16* p16, long long n, const float* hyper,
+                            float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2,
+                            const float* gscale_ptr, float gscale, float* ema, const float* omd_ptr, float omd,
+                            hipStream_t st) {
+  if (!ema) return -1;
+  hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n)), dim3(256), 0, st, p, g, m, v, p16, n, hyper, lr, b1, b2, eps,
+                     wd, decoupled, bc1, bc2, gscale_ptr, gscale, EmaArgs<true>{ema, omd_ptr, omd});
+  RET_LAST;
+}
+extern "C" int dbx_ema_update(float* e, const float* p, long long n, const float* omd_ptr, float omd,
+                              hipStream_t st) {
+  if (n <= 0) return 0;
+  hipLaunchKernelGGL(ema_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, (const EmaDesc*)nullptr, e, p, n,
+                     omd_ptr, omd);
+  RET_LAST;
+}
+extern "C" int dbx_ema_update_multi(const void* desc, int ntensors, long long max_len, const float* omd_ptr, float omd,
+                                    hipStream_t st) {
+  if (ntensors <= 0 || max_len <= 0) return 0;
+  if (!desc || ntensors > 65535) return -1;
+  hipLaunchKernelGGL(ema_kernel, dim3(grid_for((max_len + 3) / 4, 256, 64), ntensors), dim3(256), 0, st,
+                     (const EmaDesc*)desc, (float*)nullptr, (const float*)nullptr, 0LL, omd_ptr, omd);
   RET_LAST;
 }
 extern "C" int dbx_lars_scale(const float* p, float* g, const int* seg_off, const int* seg_len, const int* adapt,

@@ -55,7 +55,8 @@ class NativeTrainer:
                  bucket_cap_mb: float = 64.0, allreduce_dtype: torch.dtype = torch.float32,
                  process_group=None, src_hw: Optional[Tuple[int, int]] = None, mean=None, std=None,
                  zero_stage: int = 0, cutmix_alpha: float = 0.0, seed: int = 0,
-                 engine: Optional[EngineConfig] = None, grad_accum: int = 1):
+                 engine: Optional[EngineConfig] = None, grad_accum: int = 1, ema_decay: float = 0.0,
+                 ema_warmup: bool = False):
         self.dev = device
         self.cfg = cfg = engine if engine is not None else EngineConfig.current()
         optim = optim or OptimConfig()
@@ -64,6 +65,12 @@ class NativeTrainer:
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         if zero_stage and optim.name == "lars":
             raise ValueError("LARS runs on the full flat buffer; use zero_stage=0")
+        self.ema_decay = float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        if not 0.0 <= self.ema_decay < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay}")
+        if zero_stage and self.ema_decay > 0:
+            raise ValueError("the weight EMA is not sharded; use zero_stage=0 with ema_decay > 0")
         # ZeRO: segment groups aligned to 16 x world elements (equal per-rank parts) and a flat bf16
         # parameter copy (the all-gather target the weight preparation reads)
         self.prog = ResNetProgram(model, batch, image_hw, device, src_hw=src_hw, mean=mean, std=std,
@@ -211,6 +218,13 @@ class NativeTrainer:
             self.mom = self.zero.m  # shard-sized optimizer state only
             self.mom2 = self.zero.v
         self.lars = self._lars_segments() if optim.name == "lars" else None
+        # weight EMA (ema_decay > 0): ``ema`` shadows the flat master and is moved by the optimizer
+        # kernels themselves (fused variant); ``ema_bn`` shadows every BN's running_mean / running_var
+        # (module buffers outside the master: one table-driven launch in the optimizer phase). 1 - d_t
+        # reaches the captured step through a device scalar of its own (hyper's layout is untouched).
+        self.ema = self.ema_bn = None
+        if self.ema_decay > 0:
+            self._alloc_ema()
         self._build_phases()
         self.opt_ranges = self._optimizer_ranges()
         # broadcast initial parameters from rank 0 (DDP constructor semantics, M2)
@@ -223,8 +237,55 @@ class NativeTrainer:
                 dist.broadcast(bn.mod.running_var, src, group=process_group)
         if self.zero is not None:
             self.zero.refresh_param16()
+        if self.ema is not None:
+            self._seed_ema()
 
     # ----------------------------------------------------------------------------------
+    def _alloc_ema(self):
+        p, dev = self.prog, self.dev
+        self.ema = torch.zeros(p.n_params, device=dev)
+        # one flat buffer, [mean, var] per BN in prog.bns order, each at a 16-byte aligned offset
+        offs, o = [], 0
+        for bn in p.bns:
+            offs.append(o)
+            o += 2 * ((bn.C + 3) // 4 * 4)
+        self.ema_bn = torch.zeros(o, device=dev)
+        self.ema_bn_views = []
+        pairs = []
+        for bn, o in zip(p.bns, offs):
+            c = (bn.C + 3) // 4 * 4
+            mean, var = self.ema_bn[o:o + bn.C], self.ema_bn[o + c:o + c + bn.C]
+            self.ema_bn_views.append((mean, var))
+            pairs += [(mean, bn.mod.running_mean), (var, bn.mod.running_var)]
+            # what an evaluation from the average hands bn_eval_coeff (program._bn_fwd)
+            bn.ema_eval = (self.ema[bn.off_w:bn.off_w + bn.C], self.ema[bn.off_b:bn.off_b + bn.C], mean, var)
+        self._ema_bn_desc = K.pack_ema_desc(pairs, dev)
+        self._ema_bn_n, self._ema_bn_max = len(pairs), max(bn.C for bn in p.bns)
+        self.ema_hyper = torch.zeros(1, device=dev)  # 1 - d_t (device-side, graph-safe)
+        self._ema_hyper_dev = DeviceHyper(self.ema_hyper)
+
+    def _seed_ema(self):
+        """The average starts at (a copy of) the current parameters and running statistics."""
+        with torch.no_grad():
+            self.ema.copy_(self.prog.master)
+            for bn, (mean, var) in zip(self.prog.bns, self.ema_bn_views):
+                mean.copy_(bn.mod.running_mean)
+                var.copy_(bn.mod.running_var)
+
+    def ema_decay_at(self, t: int) -> float:
+        """The decay d_t of optimizer step ``t`` (1-based): ``ema_decay``, or with ``ema_warmup``
+        min(ema_decay, (1 + t) / (10 + t)) (the timm / TF rule)."""
+        if self.ema_warmup:
+            return min(self.ema_decay, (1.0 + t) / (10.0 + t))
+        return self.ema_decay
+
+    def _ema_kw(self, lo: int, hi: int) -> dict:
+        """The fused-average arguments of an optimizer launch over master[lo:hi] (none when off)."""
+        if self.ema is None:
+            return {}
+        return {"ema": self.ema[lo:hi], "ema_hyper": self.ema_hyper,
+                "ema_one_minus_decay": 1.0 - self.ema_decay}
+
     def _segment_ranges(self):
         """Contiguous [lo, hi) of every backward segment's gradients (None: no parameters)."""
         out = []
@@ -325,11 +386,12 @@ class NativeTrainer:
         if o.name == "sgd":
             K.sgd_step(p.master[lo:hi], p.grad[lo:hi], self.mom[lo:hi], None, lr=o.lr, momentum=o.momentum,
                        dampening=o.dampening, weight_decay=o.weight_decay, nesterov=o.nesterov, first=False,
-                       grad_scale=gscale, hyper=self.hyper)
+                       grad_scale=gscale, hyper=self.hyper, **self._ema_kw(lo, hi))
         else:
             K.adam_step(p.master[lo:hi], p.grad[lo:hi], self.mom[lo:hi], self.mom2[lo:hi], None, lr=o.lr,
                         beta1=o.betas[0], beta2=o.betas[1], eps=o.eps, weight_decay=o.weight_decay,
-                        decoupled=(o.name == "adamw"), step=1, grad_scale=gscale, hyper=self.hyper)
+                        decoupled=(o.name == "adamw"), step=1, grad_scale=gscale, hyper=self.hyper,
+                        **self._ema_kw(lo, hi))
 
     def _after_phase_updates(self, i: int):
         """Issue phase i's parameter updates (see _optimizer_ranges)."""
@@ -406,6 +468,10 @@ class NativeTrainer:
         if self.k > 1 and not self.segmented:
             # no per-range collective folded the accumulator in: once over the whole buffer
             self._fold(0, p.grad.numel())
+        if self.ema is not None:
+            # the BN running statistics are final since the forward: all 2 x len(bns) buffers, one launch
+            K.ema_update_multi(self._ema_bn_desc, self._ema_bn_n, self._ema_bn_max,
+                               one_minus_decay=1.0 - self.ema_decay, hyper=self.ema_hyper)
         if self.zero is not None:
             # ZeRO-1/2: update this rank's shard of the fp32 master with its shard of the optimizer
             # state (the reduce-scatter and the all-gather run around this phase, not inside it:
@@ -434,17 +500,18 @@ class NativeTrainer:
             K.lars_scale(p.master, p.grad, off, ln, adapt, norms, grad_scale=1.0 / gdiv,
                          eta=o.trust_coefficient, weight_decay=o.weight_decay, max_len=mx)
             K.sgd_step(p.master, p.grad, self.mom, None, lr=o.lr, momentum=o.momentum, dampening=o.dampening,
-                       weight_decay=0.0, nesterov=o.nesterov, first=False, grad_scale=1.0, hyper=self.hyper)
+                       weight_decay=0.0, nesterov=o.nesterov, first=False, grad_scale=1.0, hyper=self.hyper,
+                       **self._ema_kw(0, p.n_params))
             return
         gscale = 1.0 / gdiv
         if o.name == "sgd":
             K.sgd_step(p.master, p.grad, self.mom, None, lr=o.lr, momentum=o.momentum, dampening=o.dampening,
                        weight_decay=o.weight_decay, nesterov=o.nesterov, first=False, grad_scale_ptr=gsp,
-                       grad_scale=gscale, hyper=self.hyper)
+                       grad_scale=gscale, hyper=self.hyper, **self._ema_kw(0, p.n_params))
         else:
             K.adam_step(p.master, p.grad, self.mom, self.mom2, None, lr=o.lr, beta1=o.betas[0], beta2=o.betas[1],
                         eps=o.eps, weight_decay=o.weight_decay, decoupled=(o.name == "adamw"), step=1,
-                        grad_scale_ptr=gsp, grad_scale=gscale, hyper=self.hyper)
+                        grad_scale_ptr=gsp, grad_scale=gscale, hyper=self.hyper, **self._ema_kw(0, p.n_params))
 
     # ----------------------------------------------------------------------------------
     def _post(self, post):
@@ -526,6 +593,10 @@ class NativeTrainer:
         else:
             vals = [o.lr, 1.0 - o.betas[0] ** t, 1.0 - o.betas[1] ** t, first]
         self._hyper_dev.set(vals)
+        if self.ema is not None:
+            # 1 - d_t in double; the copy to the fp32 device scalar is its one rounding. (A micro-step
+            # launches no EMA kernel; it carries the value of the update its window ends with.)
+            self._ema_hyper_dev.set([1.0 - self.ema_decay_at(t)])
 
     @property
     def grad_accum(self) -> int:
@@ -698,10 +769,15 @@ class NativeTrainer:
     # ----------------------------------------------------------------------------------
     @torch.no_grad()
     def evaluate_batch(self, images_u8: torch.Tensor, labels: torch.Tensor,
-                       boxes: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       boxes: Optional[torch.Tensor] = None, use_ema: Optional[bool] = None) -> torch.Tensor:
         """Eval-mode forward (running BN stats); returns logits (bf16) and accumulates metrics.
-        A short final batch is padded (padding rows get label -> excluded by the caller)."""
+        A short final batch is padded (padding rows get label -> excluded by the caller).
+        ``use_ema``: evaluate the averaged weights and running statistics (None: when enabled). Nothing
+        of it outlives the call: every step and every evaluation prepares its own bf16 weights."""
         p = self.prog
+        use_ema = self.ema is not None if use_ema is None else bool(use_ema)
+        if use_ema and self.ema is None:
+            raise ValueError("use_ema=True needs a trainer built with ema_decay > 0")
         p.training = False
         if self.comm_stream is not None:  # the last step's parameter all-gather (ZeRO)
             torch.cuda.current_stream(self.dev).wait_stream(self.comm_stream)
@@ -711,11 +787,59 @@ class NativeTrainer:
         if boxes is not None:
             p.boxes[:n].copy_(boxes)
         p.flip.zero_()
-        p.prepare_weights()
+        p.prepare_weights(src=self.ema if use_ema else None)
         p.load_input_u8(None)
-        out = p.forward(smoothing=0.0, compute_grad=False, metrics=False)
-        p.training = True
+        p.eval_ema = use_ema
+        try:
+            out = p.forward(smoothing=0.0, compute_grad=False, metrics=False)
+        finally:
+            p.eval_ema = False
+            p.training = True
         return out[:n]
+
+    def _ema_maps(self):
+        """(master address, the model's parameters by name, averaged buffer by running-statistic address)."""
+        if self.ema is None:
+            raise ValueError("no weight EMA: the trainer was built with ema_decay=0")
+        p = self.prog
+        bn_of = {}
+        for bn, (mean, var) in zip(p.bns, self.ema_bn_views):
+            bn_of[bn.mod.running_mean.data_ptr()] = mean
+            bn_of[bn.mod.running_var.data_ptr()] = var
+        return p.master.data_ptr(), dict(p.model.named_parameters()), bn_of
+
+    def ema_state_dict(self) -> dict:
+        """The averaged model with the keys and shapes of ``model.state_dict()``: averaged parameters
+        and BN running statistics; everything else (num_batches_tracked) copied as it is."""
+        p = self.prog
+        base, named, bn_of = self._ema_maps()
+        out = {}
+        for key, t in p.model.state_dict().items():
+            if key in named:
+                # the module parameter is a (possibly permuted) view of the flat master: the same view of ema
+                off = (t.data_ptr() - base) // 4
+                out[key] = torch.as_strided(self.ema, t.size(), t.stride(), off).clone()
+            elif t.data_ptr() in bn_of and t.dtype == torch.float32:
+                out[key] = bn_of[t.data_ptr()].clone()
+            else:
+                out[key] = t.detach().clone()
+        return out
+
+    def load_ema_state_dict(self, sd: dict) -> None:
+        """Inverse of :meth:`ema_state_dict` (num_batches_tracked and other plain buffers are ignored)."""
+        p = self.prog
+        base, named, bn_of = self._ema_maps()
+        cur = p.model.state_dict()
+        missing = [k for k in cur if k not in sd]
+        if missing:
+            raise KeyError(f"load_ema_state_dict: missing keys {missing[:4]}{'...' if len(missing) > 4 else ''}")
+        with torch.no_grad():
+            for key, t in cur.items():
+                if key in named:
+                    off = (t.data_ptr() - base) // 4
+                    torch.as_strided(self.ema, t.size(), t.stride(), off).copy_(sd[key])
+                elif t.data_ptr() in bn_of and t.dtype == torch.float32:
+                    bn_of[t.data_ptr()].copy_(sd[key])
 
     def sync_master(self) -> None:
         """Make the module's fp32 parameters (views of the flat master) complete on every rank:
@@ -728,9 +852,11 @@ class NativeTrainer:
 
     def params_changed(self) -> None:
         """Call after writing the parameters from outside (checkpoint load): ZeRO re-derives its
-        bf16 parameter copy from the (full) fp32 master."""
+        bf16 parameter copy from the (full) fp32 master; the weight EMA restarts from the new values."""
         if self.zero is not None:
             self.zero.refresh_param16()
+        if self.ema is not None:
+            self._seed_ema()
 
     def read_metrics(self, reset: bool = True) -> Tuple[float, float]:
         m = self.prog.metrics[:2].tolist()

@@ -297,6 +297,7 @@ class ResNetProgram:
         self.build_fins()
         self._pack_step_descs()
         self.training = True
+        self.eval_ema = False  # evaluate from the trainer's weight EMA (NativeTrainer.evaluate_batch)
 
     # ----------------------------------------------------------------------------------
     # construction
@@ -707,11 +708,13 @@ class ResNetProgram:
     # ----------------------------------------------------------------------------------
     # per-step pieces
     # ----------------------------------------------------------------------------------
-    def prepare_weights(self, step: bool = False):
+    def prepare_weights(self, step: bool = False, src: Optional[torch.Tensor] = None):
         """fp32 master -> bf16 compute copies (KRSC fwd, CRSK dgrad, fc weight and bias, stem 8x8x4),
         one launch. ``step``: a training step follows -- the same launch zeroes the BN statistics and
-        counts num_batches_tracked (the forward then skips its own zeroing)."""
-        src = self.master if self.param16 is None else self.param16  # ZeRO: the all-gathered bf16 copy
+        counts num_batches_tracked (the forward then skips its own zeroing). ``src``: another flat fp32
+        buffer of the master's layout to derive them from (the trainer's weight EMA, for evaluation)."""
+        if src is None:
+            src = self.master if self.param16 is None else self.param16  # ZeRO: the all-gathered bf16 copy
         if step and self.wdesc_step is not None:
             K.weight_prep(src, self.w16buf, self.wdesc_step, self.n_wdesc_step)
             self._stats_zeroed = True
@@ -750,6 +753,9 @@ class ResNetProgram:
             mom = mod.momentum if mod.momentum is not None else 0.1
             K.bn_finalize(bn.stats, count, bn.gamma, bn.beta, mod.eps, mom if mod.track_running_stats else 0.0,
                           mod.running_mean, mod.running_var, bn.scale, bn.shift, bn.mean, bn.invstd)
+        elif self.eval_ema:  # the trainer's averaged affine parameters and running statistics
+            gamma, beta, rmean, rvar = bn.ema_eval
+            K.bn_eval_coeff(gamma, beta, mod.eps, rmean, rvar, bn.scale, bn.shift)
         else:
             K.bn_eval_coeff(bn.gamma, bn.beta, mod.eps, mod.running_mean, mod.running_var, bn.scale, bn.shift)
 

@@ -1304,14 +1304,22 @@ def dropout(x, y, p, seed, offset):
 
 @_dispatch
 def sgd_step(p, g, v, p16=None, *, lr, momentum, dampening=0.0, weight_decay=0.0, nesterov=False, first=False,
-             grad_scale_ptr=None, grad_scale=1.0, hyper=None):
-    """PyTorch-SGD semantics. ``hyper`` (fp32[1] device tensor) overrides ``lr`` at run time."""
+             grad_scale_ptr=None, grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0):
+    """PyTorch-SGD semantics. ``hyper`` (fp32[1] device tensor) overrides ``lr`` at run time. ``ema``
+    (flat fp32, the size of ``p``): the same launch also moves the weight average towards the updated
+    parameter, ``e = fma(omd, p_new - e, e)`` (see :func:`ema_update` for ``omd``)."""
     n = p.numel()
     _chk(p, torch.float32, "p")
     _chk(g, torch.float32, "g", n)
     _chk(v, torch.float32, "v", n)
     if p16 is not None:
         _chk(p16, torch.bfloat16, "p16", n)
+    if ema is not None:
+        _chk_ema(ema, n, ema_hyper)
+        C().sgd_ema(p.data_ptr(), g.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr), float(momentum),
+                    float(dampening), float(weight_decay), int(nesterov), int(first), _p(grad_scale_ptr),
+                    float(grad_scale), ema.data_ptr(), _p(ema_hyper), float(ema_one_minus_decay), stream_ptr())
+        return
     C().sgd(p.data_ptr(), g.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr), float(momentum), float(dampening),
             float(weight_decay), int(nesterov), int(first), _p(grad_scale_ptr), float(grad_scale), stream_ptr())
 
@@ -1347,13 +1355,21 @@ def lars_scale(p, g, seg_off, seg_len, adapt, norms, *, grad_scale, eta, weight_
 
 @_dispatch
 def adam_step(p, g, m, v, p16=None, *, lr, beta1, beta2, eps, weight_decay, decoupled, step,
-              grad_scale_ptr=None, grad_scale=1.0, hyper=None):
-    """Adam / AdamW. ``hyper`` (fp32[3] device: lr, 1-b1^t, 1-b2^t) overrides lr/step at run time."""
+              grad_scale_ptr=None, grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0):
+    """Adam / AdamW. ``hyper`` (fp32[3] device: lr, 1-b1^t, 1-b2^t) overrides lr/step at run time.
+    ``ema`` / ``ema_hyper`` / ``ema_one_minus_decay``: the fused weight average, as in :func:`sgd_step`."""
     n = p.numel()
     for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
         _chk(t, torch.float32, nm, n)
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
+    if ema is not None:
+        _chk_ema(ema, n, ema_hyper)
+        C().adam_ema(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr),
+                     float(beta1), float(beta2), float(eps), float(weight_decay), int(decoupled), float(bc1),
+                     float(bc2), _p(grad_scale_ptr), float(grad_scale), ema.data_ptr(), _p(ema_hyper),
+                     float(ema_one_minus_decay), stream_ptr())
+        return
     C().adam(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr), float(beta1),
              float(beta2), float(eps), float(weight_decay), int(decoupled), float(bc1), float(bc2),
              _p(grad_scale_ptr), float(grad_scale), stream_ptr())
@@ -1370,6 +1386,63 @@ def grad_accum(dst, src, *, first=False, flag=None):
         _chk(flag, torch.float32, "flag", 1)
     C().grad_accum(dst.data_ptr(), src.data_ptr(), dst.numel(), int(bool(first)), _p(flag), stream_ptr())
     return dst
+
+
+def _chk_ema(ema, n: int, ema_hyper) -> None:
+    _chk(ema, torch.float32, "ema", n)
+    if ema.data_ptr() % 16:
+        raise ValueError("ema: the fused update needs a 16-byte aligned slice (as p, g and v are)")
+    if ema_hyper is not None:
+        _chk(ema_hyper, torch.float32, "ema_hyper", 1)
+
+
+@_dispatch
+def ema_update(e, p, *, one_minus_decay=0.0, hyper=None):
+    """Weight EMA over two flat fp32 slices (any 4-byte aligned): ``e = fma(omd, p - e, e)`` in fp32.
+    ``omd`` is ``1 - decay``, computed in double by the caller and rounded to fp32 once (``1 - d`` is
+    never formed from an fp32 ``d``: at d = 0.9999 that would cost four digits). ``hyper`` (fp32[1]
+    device tensor) overrides ``one_minus_decay`` at run time, so a captured step follows a decay
+    schedule. Bit-identical to the update fused into :func:`sgd_step` / :func:`adam_step`."""
+    _chk(e, torch.float32, "e")
+    _chk(p, torch.float32, "p", e.numel())
+    if hyper is not None:
+        _chk(hyper, torch.float32, "hyper", 1)
+    C().ema_update(e.data_ptr(), p.data_ptr(), e.numel(), _p(hyper), float(one_minus_decay), stream_ptr())
+    return e
+
+
+def pack_ema_desc(pairs, device) -> torch.Tensor:
+    """Descriptor table of one :func:`ema_update_multi` launch (csrc/nn_ops.hip EmaDesc {int64 dst
+    address, src address, length} = 24 bytes per entry) from ``(dst, src)`` tensor pairs: flat fp32,
+    contiguous, equal sizes, on ``device``. The table holds raw addresses: rebuild it if a tensor it
+    names is reallocated."""
+    rows = []
+    want = torch.device(device)
+    for i, (dst, src) in enumerate(pairs):
+        for t, nm in ((dst, "dst"), (src, "src")):
+            if t.dtype != torch.float32:
+                raise TypeError(f"pack_ema_desc: entry {i} {nm}: expected torch.float32, got {t.dtype}")
+            same_dev = t.device.type == want.type and (want.index is None or t.device.index == want.index)
+            if not t.is_contiguous() or not same_dev:
+                raise ValueError(f"pack_ema_desc: entry {i} {nm}: must be contiguous and on {device}")
+        if dst.numel() != src.numel():
+            raise ValueError(f"pack_ema_desc: entry {i}: {dst.numel()} destination and {src.numel()} source elements")
+        rows.append([dst.data_ptr(), src.data_ptr(), dst.numel()])
+    return torch.tensor(rows, dtype=torch.int64).reshape(-1, 3).to(device)
+
+
+@_dispatch
+def ema_update_multi(desc, ntensors, max_len, *, one_minus_decay=0.0, hyper=None):
+    """:func:`ema_update` over every entry of a :func:`pack_ema_desc` table in ONE launch (grid =
+    (blocks, ntensors)): the BatchNorm running statistics, which are separate module buffers. Same
+    kernel, same bits as one :func:`ema_update` per entry. ``max_len``: the longest entry."""
+    if desc.dtype != torch.int64:
+        raise TypeError(f"desc: expected torch.int64, got {desc.dtype}")
+    if not desc.is_contiguous() or desc.numel() != 3 * int(ntensors):
+        raise ValueError(f"desc: expected a contiguous [{ntensors}, 3] table, got shape {tuple(desc.shape)}")
+    if hyper is not None:
+        _chk(hyper, torch.float32, "hyper", 1)
+    C().ema_update_multi(desc.data_ptr(), int(ntensors), int(max_len), _p(hyper), float(one_minus_decay), stream_ptr())
 
 
 @_dispatch

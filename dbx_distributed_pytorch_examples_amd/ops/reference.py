@@ -398,7 +398,9 @@ def softmax_ce(logits, labels, dlogits=None, loss_out=None, stats=None, smoothin
 
 
 def sgd_step(p, g, v, p16=None, *, lr, momentum, dampening=0.0, weight_decay=0.0, nesterov=False, first=False,
-             grad_scale_ptr=None, grad_scale=1.0, hyper=None):
+             grad_scale_ptr=None, grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0):
+    if ema is not None:
+        _chk_ema_pair(ema, p, "sgd_step")
     if hyper is not None:
         lr = float(hyper[0])
     gs = grad_scale * (float(grad_scale_ptr[0]) if grad_scale_ptr is not None else 1.0)
@@ -412,10 +414,14 @@ def sgd_step(p, g, v, p16=None, *, lr, momentum, dampening=0.0, weight_decay=0.0
     p.sub_(lr * d)
     if p16 is not None:
         p16.copy_(p.bfloat16())
+    if ema is not None:
+        ema_update(ema, p, one_minus_decay=ema_one_minus_decay, hyper=ema_hyper)
 
 
 def adam_step(p, g, m, v, p16=None, *, lr, beta1, beta2, eps, weight_decay, decoupled, step, grad_scale_ptr=None,
-              grad_scale=1.0, hyper=None):
+              grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0):
+    if ema is not None:
+        _chk_ema_pair(ema, p, "adam_step")
     bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
     if hyper is not None:
         lr, bc1, bc2 = float(hyper[0]), float(hyper[1]), float(hyper[2])
@@ -430,6 +436,8 @@ def adam_step(p, g, m, v, p16=None, *, lr, beta1, beta2, eps, weight_decay, deco
     p.sub_(lr * (m / bc1) / (torch.sqrt(v / bc2) + eps))
     if p16 is not None:
         p16.copy_(p.bfloat16())
+    if ema is not None:
+        ema_update(ema, p, one_minus_decay=ema_one_minus_decay, hyper=ema_hyper)
 
 
 def grad_accum(dst, src, *, first=False, flag=None):
@@ -444,6 +452,35 @@ def grad_accum(dst, src, *, first=False, flag=None):
     else:
         dst.add_(src.view_as(dst))
     return dst
+
+
+def _chk_ema_pair(e, p, what: str) -> None:
+    if e.dtype != torch.float32 or p.dtype != torch.float32:
+        raise TypeError(f"{what}: expected float32 tensors")
+    if e.numel() != p.numel() or not (e.is_contiguous() and p.is_contiguous()):
+        raise ValueError(f"{what}: the average and the parameters must be contiguous with equal numel")
+
+
+def ema_update(e, p, *, one_minus_decay=0.0, hyper=None):
+    """e += omd * (p - e) in fp32 with omd rounded to fp32 first: three roundings (difference, product,
+    sum) where the kernel's fma has two."""
+    _chk_ema_pair(e, p, "ema_update")
+    omd = float(hyper.reshape(-1)[0]) if hyper is not None else float(torch.tensor(one_minus_decay, dtype=torch.float32))
+    e.add_((p.view_as(e) - e) * omd)
+    return e
+
+
+def ema_update_multi(desc, ntensors, max_len, *, one_minus_decay=0.0, hyper=None):
+    """The table holds host addresses here: each entry is viewed in place and updated like ema_update."""
+    import ctypes
+    if desc.dtype != torch.int64 or desc.numel() != 3 * int(ntensors):
+        raise ValueError("ema_update_multi: expected an int64 [ntensors, 3] table")
+    for dst, src, n in desc.reshape(-1, 3).tolist():
+        if n <= 0:
+            continue
+        e = torch.frombuffer((ctypes.c_float * n).from_address(dst), dtype=torch.float32)
+        p = torch.frombuffer((ctypes.c_float * n).from_address(src), dtype=torch.float32)
+        ema_update(e, p, one_minus_decay=one_minus_decay, hyper=hyper)
 
 
 def global_norm_clip_factor(g, max_norm, work):

@@ -52,6 +52,7 @@ class TrainResult:
     images_per_sec: float = 0.0
     engine: str = ""
     resumed_epoch: int = 0   # > 0: this run resumed from the checkpoint of that epoch
+    ema_state_dict: Optional[Dict[str, Any]] = None  # the averaged model (cfg.ema_decay > 0), else None
 
 
 def _log(msg: str):
@@ -139,7 +140,8 @@ class _Native:
                                     bucket_cap_mb=cfg.bucket_cap_mb, allreduce_dtype=ar,
                                     src_hw=(h, w), mean=mean, std=std, zero_stage=cfg.zero.stage,
                                     cutmix_alpha=cfg.data.cutmix_alpha, seed=cfg.seed,
-                                    grad_accum=cfg.grad_accum)
+                                    grad_accum=cfg.grad_accum, ema_decay=cfg.ema_decay, ema_warmup=cfg.ema_warmup)
+        self.ema_eval = bool(cfg.ema_eval)
         if not cfg.data.augment:
             aug = AugmentSpec()
         elif (h, w) == (s, s) and s <= 64:
@@ -192,7 +194,10 @@ class _Native:
         loss, corr, n = 0.0, 0.0, 0
         seen = set()
         for img, lab, boxes, _ in ld:
-            logits = self.tr.evaluate_batch(img, lab, boxes).float()
+            if getattr(self.tr, "ema", None) is not None:  # cfg.ema_eval: validate the averaged weights
+                logits = self.tr.evaluate_batch(img, lab, boxes, use_ema=self.ema_eval).float()
+            else:
+                logits = self.tr.evaluate_batch(img, lab, boxes).float()
             loss += F.cross_entropy(logits, lab, reduction="sum").item()
             corr += (logits.argmax(1) == lab).sum().item()
             n += lab.shape[0]
@@ -320,6 +325,13 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
             train_dataset = build_dataset(d.dataset, d.root, True, None, d.image_size, cfg.num_classes,
                                           d.train_samples or 50 * cfg.batch_size * info.world_size, cfg.seed)
     engine = _pick_engine(cfg, model, train_dataset, dev)
+    if not 0.0 <= cfg.ema_decay < 1.0:
+        raise ValueError(f"ema_decay must be in [0, 1), got {cfg.ema_decay}")
+    if cfg.ema_decay > 0:
+        from ..models.wrappers import FrozenBackboneClassifier
+        if engine != "native" or isinstance(model, FrozenBackboneClassifier):
+            raise ValueError("ema_decay > 0 needs the native training step (NativeTrainer); this run would use the "
+                             f"{'frozen-backbone' if engine == 'native' else engine} engine, which keeps no weight EMA")
     runner = _Native(cfg, model, train_dataset, dev, 0) if engine == "native" else _Autograd(cfg, model, train_dataset, dev)
     spe = runner.steps_per_epoch()
     total = cfg.max_steps or (parse_duration(cfg.duration, spe, cfg.batch_size) if cfg.duration else spe * cfg.epochs)
@@ -356,7 +368,7 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
             mlflow.log_params({"batch_size": cfg.batch_size, "epochs": epochs, "learning_rate": cfg.optim.lr,
                                "model_type": cfg.model, "optimizer": cfg.optim.name, "weight_decay": cfg.optim.weight_decay,
                                "scheduler": cfg.sched.name, "num_gpus": ddist.get_world_size(), "engine": engine,
-                               "zero_stage": cfg.zero.stage, "trainer": "dbx_amd"})
+                               "zero_stage": cfg.zero.stage, "trainer": "dbx_amd", "ema_decay": cfg.ema_decay})
         _log(f"[train] engine={engine} world={ddist.get_world_size()} steps/epoch={spe} total_steps={total}")
         if cfg.grad_accum > 1 and cfg.checkpoint_dir and cfg.checkpoint_every and spe % cfg.grad_accum != 0:
             # (one iteration is one micro-batch; a checkpoint carries no accumulator)
@@ -456,6 +468,8 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
     res.steps = step
     res.images_per_sec = imgs / el if el > 0 else 0.0
     res.model = runner.model
+    if getattr(runner.tr, "ema", None) is not None:
+        res.ema_state_dict = {k: v.cpu() for k, v in runner.tr.ema_state_dict().items()}
     if is_main and log_mlflow:
         mlflow.log_metric("images_per_sec", res.images_per_sec)
         mlflow.pytorch.log_model(res.model, cfg.model_name or "model")
@@ -482,6 +496,8 @@ def _trainer_state(runner) -> Dict[str, Any]:
         st = {"kind": "native", "mom": tr.mom.detach().cpu(), "step_count": tr.step_count}
         if tr.mom2 is not None:
             st["mom2"] = tr.mom2.detach().cpu()
+        if getattr(tr, "ema", None) is not None:
+            st["ema"], st["ema_bn"] = tr.ema.detach().cpu(), tr.ema_bn.detach().cpu()
         return st
     if getattr(tr, "opt", None) is not None:
         return {"kind": "torch", "optimizer": ckpt.clean_state_dict(tr.opt.state_dict())}
@@ -534,5 +550,12 @@ def _restore_trainer_state(runner, st):
         tr.step_count = int(st.get("step_count", 0))
         if hasattr(tr, "micro"):
             tr.micro = 0  # no accumulator is saved: a partial window is dropped, the next call opens one
+        if getattr(tr, "ema", None) is not None:
+            if "ema" in st and "ema_bn" in st:
+                tr.ema.copy_(st["ema"])
+                tr.ema_bn.copy_(st["ema_bn"])
+            else:  # written without the average: it restarts from the loaded parameters (params_changed)
+                _log("[train] warning: the checkpoint carries no weight EMA; the average is re-seeded from "
+                     "the loaded parameters")
     elif st.get("kind") == "torch" and getattr(tr, "opt", None) is not None:
         tr.opt.load_state_dict(st["optimizer"])
