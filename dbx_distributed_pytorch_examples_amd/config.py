@@ -50,7 +50,7 @@ class LocalConfig:
 
 @dataclass
 class OptimizerConfig:
-    name: str = "sgd"                  # sgd | adam | adamw | lars
+    name: str = "sgd"                  # sgd | adam | adamw | lars | lamb
     lr: float = 0.1
     momentum: float = 0.9
     nesterov: bool = False
@@ -59,6 +59,9 @@ class OptimizerConfig:
     eps: float = 1e-8
     grad_clip: float = 0.0
     trust_coefficient: float = 0.001   # LARS eta
+    adapt_1d: bool = False             # LAMB: also decay and adapt BN affine parameters and biases
+    trust_min: float = 0.0             # LAMB trust-ratio clamp where adapted (0 = unbounded)
+    trust_max: float = 0.0
 
 
 @dataclass
@@ -275,8 +278,11 @@ def _ds_num(v: Any, auto: Union[int, float]) -> Union[int, float]:
 # DeepSpeed builds "Adam" / "AdamW" as its FusedAdam (adam_w_mode for "AdamW"), whose weight_decay
 # defaults to 0.0 -- not torch.optim.AdamW's 0.01 (the reference dicts omit the key,
 # `02_deepspeed/deepspeed_config.py:22-32`, so their runs do not decay); SGD: torch's defaults.
+#   "Lamb" is DeepSpeed's FusedLamb: weight decay 0.0, max_coeff 10.0, min_coeff 0.01 (its documented
+# defaults; DeepSpeed is not installed where this was written, so they are taken from its documentation).
 _DS_OPT_DEFAULTS = {"adamw": {"weight_decay": 0.0}, "adam": {"weight_decay": 0.0},
-                    "sgd": {"weight_decay": 0.0, "momentum": 0.0}}
+                    "sgd": {"weight_decay": 0.0, "momentum": 0.0},
+                    "lamb": {"weight_decay": 0.0, "max_coeff": 10.0, "min_coeff": 0.01}}
 
 
 def from_deepspeed(ds: Dict[str, Any], base: Optional[TrainConfig] = None, world_size: Optional[int] = None,
@@ -294,6 +300,11 @@ def from_deepspeed(ds: Dict[str, Any], base: Optional[TrainConfig] = None, world
       does) or, without a micro batch, defines it;
     * optimizer keys the dict omits take DeepSpeed's optimizer defaults (FusedAdam: weight decay 0.0
       for "Adam" and "AdamW"), not the TrainConfig's;
+    * ``"Lamb"`` (DeepSpeed's FusedLamb) maps ``lr, betas, eps, weight_decay`` and ``max_coeff`` /
+      ``min_coeff`` -> ``trust_max`` / ``trust_min``, with DeepSpeed's documented defaults (weight decay
+      0.0, ``max_coeff`` 10.0, ``min_coeff`` 0.01), and sets ``adapt_1d`` (FusedLamb decays and adapts
+      every tensor). DeepSpeed is not installed here: the defaults are its documentation's, unverified
+      against its code;
     * WarmupLR keeps its ``warmup_type`` ("log" when absent, DeepSpeed's default).
     """
     cfg = copy.deepcopy(base) if base is not None else TrainConfig()
@@ -331,11 +342,11 @@ def from_deepspeed(ds: Dict[str, Any], base: Optional[TrainConfig] = None, world
     opt = ds.get("optimizer")
     if opt:
         t = opt.get("type", "AdamW").lower()
-        if t not in ("adamw", "adam", "sgd", "lars"):
+        if t not in ("adamw", "adam", "sgd", "lars", "lamb"):
             raise ValueError(f"unsupported DeepSpeed optimizer type {opt.get('type')!r}")
         cfg.optim.name = t
         p = dict(_DS_OPT_DEFAULTS.get(t, {}))
-        p.update({"betas": (0.9, 0.999), "eps": 1e-8} if t in ("adamw", "adam") else {})
+        p.update({"betas": (0.9, 0.999), "eps": 1e-8} if t in ("adamw", "adam", "lamb") else {})
         p.update({k: v for k, v in opt.get("params", {}).items() if not _ds_auto(v)})
         if "lr" in p:
             cfg.optim.lr = float(p["lr"])
@@ -347,6 +358,10 @@ def from_deepspeed(ds: Dict[str, Any], base: Optional[TrainConfig] = None, world
             cfg.optim.weight_decay = float(p["weight_decay"])
         if "momentum" in p:
             cfg.optim.momentum = float(p["momentum"])
+        if t == "lamb":  # FusedLamb clamps the trust ratio to [min_coeff, max_coeff] and adapts every tensor
+            cfg.optim.trust_max = float(p["max_coeff"])
+            cfg.optim.trust_min = float(p["min_coeff"])
+            cfg.optim.adapt_1d = True
     sch = ds.get("scheduler")
     if sch:
         t = sch.get("type", "")

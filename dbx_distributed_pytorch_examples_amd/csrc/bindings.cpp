@@ -66,6 +66,11 @@ int dbx_ema_update_multi(const void*, int, long long, const float*, float, hipSt
 int dbx_sumsq(const float*, long long, double*, hipStream_t);
 int dbx_lars_scale(const float*, float*, const int*, const int*, const int*, int, int, double*, float, float, float,
                    hipStream_t);
+int dbx_lamb(float*, float*, float*, float*, bf16*, const int*, const int*, const int*, int, int, double*, const float*,
+             float, float, float, float, float, float, float, float, float, const float*, float, hipStream_t);
+int dbx_lamb_ema(float*, float*, float*, float*, bf16*, const int*, const int*, const int*, int, int, double*,
+                 const float*, float, float, float, float, float, float, float, float, float, const float*, float,
+                 float*, const float*, float, hipStream_t);
 int dbx_clip_factor(const double*, float, float*, hipStream_t);
 int dbx_normalize_u8(const unsigned char*, bf16*, const unsigned char*, int, int, int, int, float, float, float, float,
                      float, float, hipStream_t);
@@ -319,6 +324,25 @@ PYBIND11_MODULE(_C, m) {
     check(dbx_lars_scale(P<const float*>(p), P<float*>(g), P<const int*>(off), P<const int*>(len),
                          P<const int*>(adapt), nseg, max_len, P<double*>(norms), gs, eta, wd, S(st)),
           "lars_scale");
+  });
+  m.def("lamb", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t p16, uintptr_t off, uintptr_t len,
+                   uintptr_t adapt, int nseg, int max_len, uintptr_t norms, uintptr_t hyper, float lr, float b1, float b2,
+                   float eps, float wd, float bc1, float bc2, float tmin, float tmax, uintptr_t gsp, float gs,
+                   uintptr_t st) {
+    check(dbx_lamb(P<float*>(p), P<float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(p16), P<const int*>(off),
+                   P<const int*>(len), P<const int*>(adapt), nseg, max_len, P<double*>(norms), P<const float*>(hyper),
+                   lr, b1, b2, eps, wd, bc1, bc2, tmin, tmax, P<const float*>(gsp), gs, S(st)),
+          "lamb");
+  });
+  m.def("lamb_ema", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t p16, uintptr_t off, uintptr_t len,
+                       uintptr_t adapt, int nseg, int max_len, uintptr_t norms, uintptr_t hyper, float lr, float b1,
+                       float b2, float eps, float wd, float bc1, float bc2, float tmin, float tmax, uintptr_t gsp,
+                       float gs, uintptr_t ema, uintptr_t omd_ptr, float omd, uintptr_t st) {
+    check(dbx_lamb_ema(P<float*>(p), P<float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(p16), P<const int*>(off),
+                       P<const int*>(len), P<const int*>(adapt), nseg, max_len, P<double*>(norms),
+                       P<const float*>(hyper), lr, b1, b2, eps, wd, bc1, bc2, tmin, tmax, P<const float*>(gsp), gs,
+                       P<float*>(ema), P<const float*>(omd_ptr), omd, S(st)),
+          "lamb_ema");
   });
   m.def("sgd_ema", [](uintptr_t p, uintptr_t g, uintptr_t v, uintptr_t p16, long long n, uintptr_t hyper, float lr,
                       float mom, float damp, float wd, int nesterov, int first, uintptr_t gsp, float gs, uintptr_t ema,

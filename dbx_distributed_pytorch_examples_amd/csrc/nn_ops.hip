@@ -867,6 +867,142 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   }
 }
 
+// ----------------------------------------------------------------------------------------
+// LAMB (layer-wise adaptive moments, the Adam-family large-batch optimizer): per parameter tensor
+// ("segment" s, the LARS table), w the fp32 master, g the reduced flat gradient,
+// gs = gscale * (gscale_ptr ? *gscale_ptr : 1), lr / bc1 / bc2 from hyper[0..2] when given:
+//   gg = gs*g;  m = b1*m + (1-b1)*gg;  v = b2*v + (1-b2)*gg*gg
+//   r  = (m/bc1) / (sqrt(v/bc2) + eps)
+//   u  = adapt[s] ? r + wd*w : r                     (decay only where adapted)
+//   t  = adapt[s] && |w|>0 && |u|>0 ? |w|/|u| : 1    (L2 norms over the tensor)
+//   t  = clamp(t, trust_min, trust_max)              (only where adapted; a bound of 0 is no bound)
+//   w -= lr * t * u
+// Bias correction is always on. Two launches on the grid (blocks, nseg) of LARS, the same blocks for
+// both: lamb_moments_kernel updates m and v, leaves u IN PLACE OVER g (the gradient is dead
+// afterwards, as under LARS) and reduces |w|^2 and |u|^2 per block (fp32 lane sums, wave shuffles, one
+// LDS step over the 4 waves) into one fp64 pair per (segment, block) slot of ``norms`` -- no atomics;
+// lamb_apply_kernel sums a segment's slots in block order (every block the same fixed order: the trust
+// ratios are bit-reproducible whatever order the blocks ran in), forms t and updates w (+ the optional
+// bf16 copy, + the weight EMA from the parameter it stores in the EMA variant). 16 B per lane: every
+// segment offset is a multiple of 4 elements from 16-byte aligned bases (the wrapper checks); the
+// len % 4 tail is scalar.
+// ----------------------------------------------------------------------------------------
+__device__ __forceinline__ float lamb_u(float w, float gg, float& m, float& v, float b1, float b2, float eps, float wd,
+                                        float bc1, float bc2) {
+  m = b1 * m + (1.f - b1) * gg;
+  v = b2 * v + (1.f - b2) * gg * gg;
+  return (m / bc1) / (sqrtf(v / bc2) + eps) + wd * w;
+}
+
+__global__ __launch_bounds__(256) void lamb_moments_kernel(
+    const float* __restrict__ p, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+    const int* __restrict__ seg_off, const int* __restrict__ seg_len, const int* __restrict__ adapt,
+    const float* __restrict__ hyper, float b1, float b2, float eps, float wd, float bc1, float bc2,
+    const float* __restrict__ gscale_ptr, float gscale, double* __restrict__ norms) {
+  if (hyper) { bc1 = hyper[1]; bc2 = hyper[2]; }
+  const int s = blockIdx.y;
+  const int off = seg_off[s], len = seg_len[s];
+  if (!adapt[s]) wd = 0.f;  // (u = r + 0*w = r)
+  const float gs = gscale_ptr ? gscale * gscale_ptr[0] : gscale;
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
+  const int n4 = len / 4;
+  float ww = 0.f, uu = 0.f;
+  for (int i = tid; i < n4; i += nth) {
+    const size_t e = (size_t)off + 4 * (size_t)i;
+    const f32x4 pp = *reinterpret_cast<const f32x4*>(p + e);
+    const f32x4 gg = *reinterpret_cast<const f32x4*>(g + e) * gs;
+    f32x4 mm = *reinterpret_cast<const f32x4*>(m + e);
+    f32x4 vv = *reinterpret_cast<const f32x4*>(v + e);
+    f32x4 u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float mj = mm[j], vj = vv[j];
+      u[j] = lamb_u(pp[j], gg[j], mj, vj, b1, b2, eps, wd, bc1, bc2);
+      mm[j] = mj; vv[j] = vj;
+      ww += pp[j] * pp[j];
+      uu += u[j] * u[j];
+    }
+    *reinterpret_cast<f32x4*>(m + e) = mm;
+    *reinterpret_cast<f32x4*>(v + e) = vv;
+    *reinterpret_cast<f32x4*>(g + e) = u;
+  }
+  for (int k = n4 * 4 + tid; k < len; k += nth) {
+    const size_t e = (size_t)off + k;
+    const float w = p[e];
+    float mj = m[e], vj = v[e];
+    const float u = lamb_u(w, g[e] * gs, mj, vj, b1, b2, eps, wd, bc1, bc2);
+    m[e] = mj; v[e] = vj; g[e] = u;
+    ww += w * w;
+    uu += u * u;
+  }
+  ww = wave_sum(ww);
+  uu = wave_sum(uu);
+  __shared__ float red[2][4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (lane == 0) {
+    red[0][wave] = ww;
+    red[1][wave] = uu;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {  // slot (s, block): norms is [nseg][kLarsMaxBlocks][2], every block writes its own
+    double* o = norms + 2 * ((size_t)s * kLarsMaxBlocks + blockIdx.x);
+    o[0] = (double)(red[0][0] + red[0][1] + red[0][2] + red[0][3]);
+    o[1] = (double)(red[1][0] + red[1][1] + red[1][2] + red[1][3]);
+  }
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void lamb_apply_kernel(
+    float* __restrict__ p, const float* __restrict__ u, bf16* __restrict__ p16, const int* __restrict__ seg_off,
+    const int* __restrict__ seg_len, const int* __restrict__ adapt, const double* __restrict__ norms,
+    const float* __restrict__ hyper, float lr, float trust_min, float trust_max, EmaArgs<EMA> ea) {
+  if (hyper) lr = hyper[0];
+  [[maybe_unused]] float* __restrict__ ema = nullptr;
+  [[maybe_unused]] float omd = 0.f;
+  if constexpr (EMA) {
+    ema = ea.e;
+    omd = ea.omd_ptr ? ea.omd_ptr[0] : ea.omd;
+  }
+  const int s = blockIdx.y;
+  const int off = seg_off[s], len = seg_len[s];
+  float t = 1.f;
+  if (adapt[s]) {
+    double ww = 0.0, uu = 0.0;  // fixed block order (gridDim.x slots written by lamb_moments_kernel)
+    const double* o = norms + 2 * (size_t)s * kLarsMaxBlocks;
+    for (int b = 0; b < (int)gridDim.x; ++b) { ww += o[2 * b]; uu += o[2 * b + 1]; }
+    const float wn = (float)sqrt(ww), un = (float)sqrt(uu);
+    if (wn > 0.f && un > 0.f) t = wn / un;
+    if (trust_min > 0.f) t = fmaxf(t, trust_min);
+    if (trust_max > 0.f) t = fminf(t, trust_max);
+  }
+  const float step = lr * t;
+  const int tid = blockIdx.x * blockDim.x + threadIdx.x, nth = gridDim.x * blockDim.x;
+  const int n4 = len / 4;
+  for (int i = tid; i < n4; i += nth) {
+    const size_t e = (size_t)off + 4 * (size_t)i;
+    f32x4 pp = *reinterpret_cast<f32x4*>(p + e);
+    pp -= step * *reinterpret_cast<const f32x4*>(u + e);
+    *reinterpret_cast<f32x4*>(p + e) = pp;
+    if (p16) {
+      bf16x4 b = {(bf16)pp[0], (bf16)pp[1], (bf16)pp[2], (bf16)pp[3]};
+      *reinterpret_cast<bf16x4*>(p16 + e) = b;
+    }
+    if constexpr (EMA) {
+      f32x4 ee = *reinterpret_cast<f32x4*>(ema + e);
+      ee = f32x4{ema_lerp(ee[0], pp[0], omd), ema_lerp(ee[1], pp[1], omd), ema_lerp(ee[2], pp[2], omd),
+                 ema_lerp(ee[3], pp[3], omd)};
+      *reinterpret_cast<f32x4*>(ema + e) = ee;
+    }
+  }
+  for (int k = n4 * 4 + tid; k < len; k += nth) {
+    const size_t e = (size_t)off + k;
+    const float pp = p[e] - step * u[e];
+    p[e] = pp;
+    if (p16) p16[e] = (bf16)pp;
+    if constexpr (EMA) ema[e] = ema_lerp(ema[e], pp, omd);
+  }
+}
+
 // Gradient accumulation over the flat fp32 gradient: dst = first ? src : dst + src. ``flag`` (device,
 // nullable) overrides ``first`` at run time (first = flag[0] != 0), so one captured micro-step serves
 // every position of an accumulation window; in first mode dst is never read (stale NaN / Inf in the
@@ -1333,6 +1469,38 @@ extern "C" int dbx_lars_scale(const float* p, float* g, const int* seg_off, cons
   hipLaunchKernelGGL(lars_apply_kernel, dim3(bx, nseg), dim3(256), 0, st, p, g, seg_off, seg_len, adapt, norms, gs,
                      eta, wd);
   RET_LAST;
+}
+// LAMB: both kernels on one grid (the slots the second reads are the ones the first wrote)
+template <bool EMA>
+static int lamb_launch(float* p, float* g, float* m, float* v, bf16* p16, const int* seg_off, const int* seg_len,
+                       const int* adapt, int nseg, int max_len, double* norms, const float* hyper, float lr, float b1,
+                       float b2, float eps, float wd, float bc1, float bc2, float trust_min, float trust_max,
+                       const float* gscale_ptr, float gscale, EmaArgs<EMA> ea, hipStream_t st) {
+  if (nseg <= 0) return 0;
+  if (nseg > 65535 || !seg_off || !seg_len || !adapt || !norms) return -1;
+  int bx = (int)((max_len + 255) / 256);
+  bx = bx < 1 ? 1 : (bx > kLarsMaxBlocks ? kLarsMaxBlocks : bx);
+  hipLaunchKernelGGL(lamb_moments_kernel, dim3(bx, nseg), dim3(256), 0, st, p, g, m, v, seg_off, seg_len, adapt, hyper,
+                     b1, b2, eps, wd, bc1, bc2, gscale_ptr, gscale, norms);
+  hipLaunchKernelGGL(lamb_apply_kernel<EMA>, dim3(bx, nseg), dim3(256), 0, st, p, g, p16, seg_off, seg_len, adapt,
+                     norms, hyper, lr, trust_min, trust_max, ea);
+  RET_LAST;
+}
+extern "C" int dbx_lamb(float* p, float* g, float* m, float* v, bf16* p16, const int* seg_off, const int* seg_len,
+                        const int* adapt, int nseg, int max_len, double* norms, const float* hyper, float lr, float b1,
+                        float b2, float eps, float wd, float bc1, float bc2, float trust_min, float trust_max,
+                        const float* gscale_ptr, float gscale, hipStream_t st) {
+  return lamb_launch<false>(p, g, m, v, p16, seg_off, seg_len, adapt, nseg, max_len, norms, hyper, lr, b1, b2, eps, wd,
+                            bc1, bc2, trust_min, trust_max, gscale_ptr, gscale, EmaArgs<false>{}, st);
+}
+extern "C" int dbx_lamb_ema(float* p, float* g, float* m, float* v, bf16* p16, const int* seg_off, const int* seg_len,
+                            const int* adapt, int nseg, int max_len, double* norms, const float* hyper, float lr,
+                            float b1, float b2, float eps, float wd, float bc1, float bc2, float trust_min,
+                            float trust_max, const float* gscale_ptr, float gscale, float* ema, const float* omd_ptr,
+                            float omd, hipStream_t st) {
+  if (!ema) return -1;
+  return lamb_launch<true>(p, g, m, v, p16, seg_off, seg_len, adapt, nseg, max_len, norms, hyper, lr, b1, b2, eps, wd,
+                           bc1, bc2, trust_min, trust_max, gscale_ptr, gscale, EmaArgs<true>{ema, omd_ptr, omd}, st);
 }
 extern "C" int dbx_grad_accum(float* dst, const float* src, long long n, int first, const float* flag,
                               hipStream_t st) {

@@ -51,7 +51,50 @@ class LARS(torch.optim.Optimizer):
                 p.add_(d, alpha=-grp["lr"])
 
 
+class LAMB(torch.optim.Optimizer):
+    """LAMB (You et al., layer-wise adaptive moments): Adam moments with bias correction, r = mhat /
+    (sqrt(vhat) + eps); tensors with ndim > 1 (every tensor with ``adapt_1d``) take u = r + wd*w and the
+    trust ratio t = |w|/|u| (1 when either norm is 0), clamped to [trust_min, trust_max] (a bound of 0 is
+    no bound); the others take u = r, t = 1; w -= lr*t*u. Same math as the native ``lamb_step`` kernels."""
+
+    def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adapt_1d=False, trust_min=0.0,
+                 trust_max=0.0):
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
+                                      adapt_1d=bool(adapt_1d), trust_min=trust_min, trust_max=trust_max))
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        for grp in self.param_groups:
+            b1, b2 = grp["betas"]
+            for p in grp["params"]:
+                if p.grad is None:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st["step"] = 0
+                    st["exp_avg"], st["exp_avg_sq"] = torch.zeros_like(p), torch.zeros_like(p)
+                st["step"] += 1
+                m, v, g = st["exp_avg"], st["exp_avg_sq"], p.grad
+                m.mul_(b1).add_(g, alpha=1 - b1)
+                v.mul_(b2).addcmul_(g, g, value=1 - b2)
+                u = (m / (1 - b1 ** st["step"])) / (torch.sqrt(v / (1 - b2 ** st["step"])) + grp["eps"])
+                if p.ndim > 1 or grp["adapt_1d"]:
+                    u = u + grp["weight_decay"] * p
+                    wn, un = p.norm(), u.norm()
+                    t = torch.where((wn > 0) & (un > 0), wn / un, torch.ones_like(wn))
+                    if grp["trust_min"] > 0:
+                        t = t.clamp(min=grp["trust_min"])
+                    if grp["trust_max"] > 0:
+                        t = t.clamp(max=grp["trust_max"])
+                    u = u * t
+                p.add_(u, alpha=-grp["lr"])
+
+
 def build_torch_optimizer(params, o):
+    if o.name == "lamb":
+        return LAMB(params, lr=o.lr, betas=tuple(o.betas), eps=o.eps, weight_decay=o.weight_decay,
+                    adapt_1d=getattr(o, "adapt_1d", False), trust_min=getattr(o, "trust_min", 0.0),
+                    trust_max=getattr(o, "trust_max", 0.0))
     if o.name == "lars":
         return LARS(params, lr=o.lr, momentum=o.momentum, weight_decay=o.weight_decay,
                     trust_coefficient=getattr(o, "trust_coefficient", 0.001), nesterov=o.nesterov)

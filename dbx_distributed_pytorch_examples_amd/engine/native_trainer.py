@@ -2,7 +2,7 @@
 
 One ``NativeTrainer.step()`` = input normalisation (uint8 -> bf16 NHWC4), forward, softmax-CE,
 backward, gradient all-reduce (world > 1) and the optimizer update (SGD-momentum / Adam /
-AdamW over the flat fp32 master, then the bf16 weight copies are re-derived next step).
+AdamW / LARS / LAMB over the flat fp32 master, then the bf16 weight copies are re-derived next step).
 
 Graphs. With world_size == 1 the whole step is ONE captured graph. With world_size > 1 the
 step is captured as segments cut where gradient buckets become final (head+layer4 | layer3 |
@@ -37,7 +37,7 @@ from .program import ResNetProgram, release_dead_graphs
 
 @dataclass
 class OptimConfig:
-    name: str = "sgd"            # sgd | adam | adamw
+    name: str = "sgd"            # sgd | adam | adamw | lars | lamb
     lr: float = 0.1
     momentum: float = 0.9
     dampening: float = 0.0
@@ -47,6 +47,9 @@ class OptimConfig:
     eps: float = 1e-8
     grad_clip: float = 0.0       # global-norm clip (DeepSpeed "gradient_clipping")
     trust_coefficient: float = 0.001  # LARS eta (name="lars")
+    adapt_1d: bool = False       # LAMB: also decay and adapt BN affine parameters and biases (FusedLamb / apex)
+    trust_min: float = 0.0       # LAMB trust-ratio clamp where adapted (0 = unbounded)
+    trust_max: float = 0.0
 
 
 class NativeTrainer:
@@ -65,6 +68,8 @@ class NativeTrainer:
         self.world = dist.get_world_size(process_group) if (dist.is_available() and dist.is_initialized()) else 1
         if zero_stage and optim.name == "lars":
             raise ValueError("LARS runs on the full flat buffer; use zero_stage=0")
+        if zero_stage and optim.name == "lamb":
+            raise ValueError("LAMB needs every tensor's norms on the full flat buffer; use zero_stage=0")
         self.ema_decay = float(ema_decay)
         self.ema_warmup = bool(ema_warmup)
         if not 0.0 <= self.ema_decay < 1.0:
@@ -89,7 +94,7 @@ class NativeTrainer:
             self.prog.enable_cutmix()
         n = self.prog.n_params
         self.mom = torch.zeros(n, device=device)
-        self.mom2 = torch.zeros(n, device=device) if optim.name in ("adam", "adamw") else None
+        self.mom2 = torch.zeros(n, device=device) if optim.name in ("adam", "adamw", "lamb") else None
         self.hyper = torch.zeros(4, device=device)      # lr, bc1, bc2, window-start flag (device-side, graph-safe)
         self._hyper_dev = DeviceHyper(self.hyper)
         self.clip_work = torch.zeros(4, device=device)
@@ -218,6 +223,7 @@ class NativeTrainer:
             self.mom = self.zero.m  # shard-sized optimizer state only
             self.mom2 = self.zero.v
         self.lars = self._lars_segments() if optim.name == "lars" else None
+        self.lamb = self._lars_segments(adapt_all=optim.adapt_1d) if optim.name == "lamb" else None
         # weight EMA (ema_decay > 0): ``ema`` shadows the flat master and is moved by the optimizer
         # kernels themselves (fused variant); ``ema_bn`` shadows every BN's running_mean / running_var
         # (module buffers outside the master: one table-driven launch in the optimizer phase). 1 - d_t
@@ -352,12 +358,12 @@ class NativeTrainer:
         serial update of every parameter. Per phase the ranges to update after it; the last phase's
         (and layer1's, whose last block's tail weight gradients run on the main stream after the stem
         backward) go on the main stream after the final join; element ranges no segment covers are
-        updated in the optimizer phase. Off (None) for clipping / LARS (global norms), ZeRO (its own
+        updated in the optimizer phase. Off (None) for clipping / LARS / LAMB (global or per-tensor norms), ZeRO (its own
         sharded update), the c10d per-segment graphs and the batched side-stream layouts."""
         p, cfg = self.prog, self.cfg
         if self.k > 1:  # (the accumulator is folded in at the top of the optimizer phase)
             return None
-        if not (cfg.overlap_optimizer != 0 and self.zero is None and self.lars is None
+        if not (cfg.overlap_optimizer != 0 and self.zero is None and self.lars is None and self.lamb is None
                 and not (self.opt.grad_clip and self.opt.grad_clip > 0)
                 and p.side_block and p.overlap_wgrad and (not self.segmented or self.block_posts)):
             return None
@@ -444,15 +450,17 @@ class NativeTrainer:
                            (rgs[0][0], rgs[-1][1]) if rgs else None))
         return merged
 
-    def _lars_segments(self):
-        """Per-tensor segments of the flat buffer for LARS; conv / fc weights are adapted (and decayed),
-        BN affine parameters and biases are not (the usual large-batch recipe)."""
+    def _lars_segments(self, adapt_all: bool = False):
+        """Per-tensor segments of the flat buffer for LARS and LAMB; conv / fc weights are adapted (and
+        decayed), BN affine parameters and biases are not (the usual large-batch recipe) unless
+        ``adapt_all`` (LAMB's ``adapt_1d``: every tensor, as DeepSpeed's FusedLamb and apex do)."""
         rs = self.prog.param_ranges
         dev = self.dev
         off = torch.tensor([r[1] for r in rs], dtype=torch.int32, device=dev)
         ln = torch.tensor([r[2] for r in rs], dtype=torch.int32, device=dev)
         bn_names = {f"{bn.name}." for bn in self.prog.bns}
-        adapt = torch.tensor([int(r[0].endswith(".weight") and not any(r[0].startswith(b) for b in bn_names))
+        adapt = torch.tensor([int(adapt_all or
+                                  (r[0].endswith(".weight") and not any(r[0].startswith(b) for b in bn_names)))
                               for r in rs], dtype=torch.int32, device=dev)
         return off, ln, adapt, torch.zeros(K.LARS_MAX_BLOCKS * 2 * len(rs), device=dev, dtype=torch.float64), max(r[2] for r in rs)
 
@@ -504,6 +512,15 @@ class NativeTrainer:
                        **self._ema_kw(0, p.n_params))
             return
         gscale = 1.0 / gdiv
+        if self.lamb is not None:
+            # one call over the whole flat buffer; the clip factor multiplies the gradient scale through
+            # the pointer, as on the Adam path (the moments see the clipped gradient)
+            off, ln, adapt, norms, mx = self.lamb
+            K.lamb_step(p.master, p.grad, self.mom, self.mom2, off, ln, adapt, norms, None, lr=o.lr,
+                        beta1=o.betas[0], beta2=o.betas[1], eps=o.eps, weight_decay=o.weight_decay, step=1,
+                        trust_min=o.trust_min, trust_max=o.trust_max, grad_scale_ptr=gsp, grad_scale=gscale,
+                        hyper=self.hyper, max_len=mx, **self._ema_kw(0, p.n_params))
+            return
         if o.name == "sgd":
             K.sgd_step(p.master, p.grad, self.mom, None, lr=o.lr, momentum=o.momentum, dampening=o.dampening,
                        weight_decay=o.weight_decay, nesterov=o.nesterov, first=False, grad_scale_ptr=gsp,

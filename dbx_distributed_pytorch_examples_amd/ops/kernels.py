@@ -1375,6 +1375,69 @@ def adam_step(p, g, m, v, p16=None, *, lr, beta1, beta2, eps, weight_decay, deco
              _p(grad_scale_ptr), float(grad_scale), stream_ptr())
 
 
+def _chk_segments(seg_off, seg_len, adapt, n: int, what: str) -> int:
+    """The segment table of :func:`lamb_step`: int32 [nseg] each, every offset a multiple of 4 elements
+    (16 B per lane from 16-byte aligned bases), every segment inside the flat buffer. Reads the table
+    on the host: call outside graph capture with a new table (the trainers build it once)."""
+    nseg = seg_off.numel()
+    for t, nm in ((seg_off, "seg_off"), (seg_len, "seg_len"), (adapt, "adapt")):
+        _chk(t, torch.int32, nm, nseg)
+    # validated once per table: the verdict rides on the seg_off tensor object (with the seg_len object
+    # and both version counters), so a replayed or captured step never reads the table back
+    ok = getattr(seg_off, "_dbx_seg_ok", None)
+    if ok is None or ok[0] != seg_off._version or ok[1] is not seg_len or ok[2] != seg_len._version or ok[3] != n:
+        off, ln = seg_off.tolist(), seg_len.tolist()
+        if any(o % 4 for o in off):
+            raise ValueError(f"{what}: every segment offset must be a multiple of 4 elements")
+        if any(o < 0 or l < 0 or o + l > n for o, l in zip(off, ln)):
+            raise ValueError(f"{what}: a segment lies outside the {n}-element buffer")
+        seg_off._dbx_seg_ok = (seg_off._version, seg_len, seg_len._version, n)
+    return nseg
+
+
+@_dispatch
+def lamb_step(p, g, m, v, seg_off, seg_len, adapt, norms, p16=None, *, lr, beta1, beta2, eps, weight_decay, step,
+              trust_min=0.0, trust_max=0.0, grad_scale_ptr=None, grad_scale=1.0, hyper=None, max_len, ema=None,
+              ema_hyper=None, ema_one_minus_decay=0.0):
+    """LAMB over the flat master, per segment s (``seg_off`` / ``seg_len`` / ``adapt``: int32 [nseg], the
+    :func:`lars_scale` table with offsets that are multiples of 4): gg = gs*g; m = b1 m + (1-b1) gg;
+    v = b2 v + (1-b2) gg^2; r = (m/bc1)/(sqrt(v/bc2) + eps); u = r + wd*w where ``adapt[s]`` else r;
+    t = |w|/|u| where ``adapt[s]`` and both norms are positive, else 1, clamped to [trust_min, trust_max]
+    where adapted (a bound of 0 is no bound); w -= lr*t*u. ``g`` holds u afterwards. ``norms``: fp64
+    [nseg*64*2] scratch (one (|w|^2, |u|^2) partial pair per segment and block, summed in fixed block
+    order: bit-reproducible). ``hyper`` (fp32[3] device: lr, 1-b1^t, 1-b2^t) overrides lr / step at run
+    time; ``grad_scale_ptr`` multiplies ``grad_scale`` (the clip factor). ``ema`` / ``ema_hyper`` /
+    ``ema_one_minus_decay``: the fused weight average, as in :func:`sgd_step`."""
+    n = p.numel()
+    for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+        _chk(t, torch.float32, nm, n)
+        if t.data_ptr() % 16:
+            raise ValueError(f"{nm}: lamb_step needs a 16-byte aligned slice")
+    if p16 is not None:
+        _chk(p16, torch.bfloat16, "p16", n)
+        if p16.data_ptr() % 8:
+            raise ValueError("p16: lamb_step needs an 8-byte aligned slice")
+    nseg = _chk_segments(seg_off, seg_len, adapt, n, "lamb_step")
+    _chk(norms, torch.float64, "norms", LARS_MAX_BLOCKS * 2 * nseg)
+    if hyper is not None:
+        _chk(hyper, torch.float32, "hyper")
+        if hyper.numel() < 3:
+            raise ValueError(f"hyper: expected at least 3 elements (lr, 1-b1^t, 1-b2^t), got {hyper.numel()}")
+    if grad_scale_ptr is not None:
+        _chk(grad_scale_ptr, torch.float32, "grad_scale_ptr", 1)
+    bc1 = 1.0 - beta1 ** step
+    bc2 = 1.0 - beta2 ** step
+    args = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p16), seg_off.data_ptr(), seg_len.data_ptr(),
+            adapt.data_ptr(), nseg, int(max_len), norms.data_ptr(), _p(hyper), float(lr), float(beta1), float(beta2),
+            float(eps), float(weight_decay), float(bc1), float(bc2), float(trust_min), float(trust_max),
+            _p(grad_scale_ptr), float(grad_scale))
+    if ema is not None:
+        _chk_ema(ema, n, ema_hyper)
+        C().lamb_ema(*args, ema.data_ptr(), _p(ema_hyper), float(ema_one_minus_decay), stream_ptr())
+        return
+    C().lamb(*args, stream_ptr())
+
+
 @_dispatch
 def grad_accum(dst, src, *, first=False, flag=None):
     """Gradient accumulation: dst = src when ``first`` else dst + src (flat fp32, any 4-byte aligned

@@ -135,7 +135,9 @@ class _Native:
             self.tr = NativeTrainer(model, cfg.batch_size, (s, s), dev,
                                     optim=OptimConfig(o.name, o.lr, o.momentum, 0.0, o.nesterov, o.weight_decay,
                                                       tuple(o.betas), o.eps, o.grad_clip,
-                                                      trust_coefficient=o.trust_coefficient),
+                                                      trust_coefficient=o.trust_coefficient,
+                                                      adapt_1d=o.adapt_1d, trust_min=o.trust_min,
+                                                      trust_max=o.trust_max),
                                     label_smoothing=cfg.data.label_smoothing, use_graphs=cfg.graphs,
                                     bucket_cap_mb=cfg.bucket_cap_mb, allreduce_dtype=ar,
                                     src_hw=(h, w), mean=mean, std=std, zero_stage=cfg.zero.stage,

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Run-to-run determinism of the native training step (world 1): the same seed and data must give
 bit-identical master weights across two eager runs and between the graph-captured and eager paths.
-  python tools/determinism_check.py [--model resnet18] [--batch 16] [--hw 32] [--steps 4] [--optim sgd|lars|adamw]
+  python tools/determinism_check.py [--model resnet18] [--batch 16] [--hw 32] [--steps 4] [--optim sgd|lars|adamw|lamb]
 """
 import argparse
 import os
@@ -17,7 +17,7 @@ from dbx_distributed_pytorch_examples_amd.models import build_model  # noqa: E40
 def run(a, use_graphs):
     torch.manual_seed(0)
     m = build_model(a.model, num_classes=10)
-    lr = {"sgd": 0.05, "lars": 2.0, "adamw": 1e-3}[a.optim]
+    lr = {"sgd": 0.05, "lars": 2.0, "adamw": 1e-3, "lamb": 2e-3}[a.optim]
     tr = NativeTrainer(m, a.batch, (a.hw, a.hw), torch.device("cuda:0"), optim=OptimConfig(name=a.optim, lr=lr),
                        use_graphs=use_graphs)
     w0 = tr.prog.master.detach().clone()
@@ -36,7 +36,7 @@ def main():
     p.add_argument("--batch", type=int, default=16)
     p.add_argument("--hw", type=int, default=32)
     p.add_argument("--steps", type=int, default=4)
-    p.add_argument("--optim", default="sgd", choices=["sgd", "lars", "adamw"])
+    p.add_argument("--optim", default="sgd", choices=["sgd", "lars", "adamw", "lamb"])
     p.add_argument("--strict", action="store_true", help="fail unless bit-identical")
     a = p.parse_args()
     w0, e1 = run(a, False)
