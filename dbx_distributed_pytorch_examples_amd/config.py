@@ -135,6 +135,8 @@ class TrainConfig:
     allreduce_dtype: str = "fp32"
     log_every: int = 100
     eval_every: int = 1
+    eval_topk: int = 5                 # val_top{k}_accuracy next to val_accuracy (0 = off; k is clipped to num_classes)
+    eval_graph: bool = True            # native engine: validation as one captured graph with device-side metrics
     patience: int = 0                  # early stopping (02_tiny_imagenet_deepspeed_resnet.py:289-297)
     checkpoint_dir: str = ""
     checkpoint_every: int = 1

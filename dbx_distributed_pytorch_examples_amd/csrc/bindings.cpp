@@ -31,6 +31,8 @@ int dbx_stem_bwd(dbx::StemBwdArgs* a, long long ws_cap, int fused, hipStream_t s
 int dbx_bn_finalize(const double*, int, int, float, const float*, const float*, float, float, float*, float*, float*,
                     float*, float*, float*, hipStream_t);
 int dbx_bn_eval_coeff(int, const float*, const float*, float, const float*, const float*, float*, float*, hipStream_t);
+int dbx_bn_eval_coeff_multi(const void*, int, int, hipStream_t);
+int dbx_ce_eval(const void*, int, const long long*, double*, int, int, int, const int*, float*, int*, hipStream_t);
 int dbx_channel_stats(const bf16*, long long, int, double*, int, hipStream_t);
 int dbx_bn_apply(const bf16*, const float*, const float*, const bf16*, const float*, const float*, bf16*, long long, int,
                  int, int, unsigned char*, hipStream_t, const dbx::BnFin*, const dbx::BnFin*);
@@ -230,6 +232,15 @@ PYBIND11_MODULE(_C, m) {
     check(dbx_bn_eval_coeff(C, P<const float*>(gamma), P<const float*>(beta), eps, P<const float*>(rm),
                             P<const float*>(rv), P<float*>(scale), P<float*>(shift), S(st)),
           "bn_eval_coeff");
+  });
+  m.def("bn_eval_coeff_multi", [](uintptr_t desc, int nbn, int max_c, uintptr_t st) {
+    check(dbx_bn_eval_coeff_multi(P<const void*>(desc), nbn, max_c, S(st)), "bn_eval_coeff_multi");
+  });
+  m.def("ce_eval", [](uintptr_t logits, int is_bf16, uintptr_t labels, uintptr_t stats, int B, int C, int k,
+                      uintptr_t nvalid, uintptr_t loss_out, uintptr_t rank_out, uintptr_t st) {
+    check(dbx_ce_eval(P<const void*>(logits), is_bf16, P<const long long*>(labels), P<double*>(stats), B, C, k,
+                      P<const int*>(nvalid), P<float*>(loss_out), P<int*>(rank_out), S(st)),
+          "ce_eval");
   });
   m.def("channel_stats", [](uintptr_t y, long long M, int C, uintptr_t stats, int nshard, uintptr_t st) {
     check(dbx_channel_stats(P<const bf16*>(y), M, C, P<double*>(stats), nshard, S(st)), "channel_stats");

@@ -12,6 +12,8 @@
 //     the masked gradient for the residual branch) using 3 per-channel coefficients;
 //   * maxpool consumes the stem's raw conv output with BN-apply+ReLU in its prologue;
 //   * softmax-cross-entropy, label smoothing, argmax/correct-count and dlogits in one kernel;
+//   * evaluation: loss + label rank (top-1 / top-k counts) in one kernel without a gradient (ce_eval),
+//     every BatchNorm's eval coefficients in one table-driven launch (bn_eval_coeff_multi);
 //   * SGD-momentum / Adam(W) over the flat fp32 master buffer, writing the bf16 compute copy.
 #include "common.h"
 #include "bn_fin.h"
@@ -65,6 +67,27 @@ __global__ void bn_eval_coeff_kernel(int C, const float* gamma, const float* bet
   const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
   scale[c] = g * inv;
   shift[c] = b - rm[c] * g * inv;
+}
+
+// The same for every BatchNorm of a model in ONE launch: a device table of descriptors, grid
+// (blocks, n_bn) with blockIdx.y the entry (built as ema_kernel's table is). gamma / beta may be null
+// (0) per entry. The per-element expression is bn_eval_coeff_kernel's: bit-identical results.
+struct BnEvalDesc { long long gamma, beta, rm, rv, scale, shift; int C; float eps; };  // 56 bytes
+__global__ void bn_eval_coeff_multi_kernel(const BnEvalDesc* __restrict__ desc) {
+  const BnEvalDesc d = desc[blockIdx.y];
+  const float* gamma = reinterpret_cast<const float*>(d.gamma);
+  const float* beta = reinterpret_cast<const float*>(d.beta);
+  const float* rm = reinterpret_cast<const float*>(d.rm);
+  const float* rv = reinterpret_cast<const float*>(d.rv);
+  float* scale = reinterpret_cast<float*>(d.scale);
+  float* shift = reinterpret_cast<float*>(d.shift);
+  const float eps = d.eps;
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < d.C; c += gridDim.x * blockDim.x) {
+    const float inv = rsqrtf(rv[c] + eps);
+    const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
+    scale[c] = g * inv;
+    shift[c] = b - rm[c] * g * inv;
+  }
 }
 
 // Channel sums of a bf16 [M][C] tensor (stats pass for layers whose producer cannot emit them)
@@ -708,6 +731,71 @@ __global__ void softmax_ce_kernel(const T* __restrict__ logits, const long long*
 }
 
 // ----------------------------------------------------------------------------------------
+// Evaluation metrics of a [B][C] logits matrix: no gradient, no smoothing. One wave per row (a
+// 1000-class bf16 row is 2 KB: 16 elements per lane, wave shuffles only), four rows per block.
+//   rank = #{c : x_c > x_l} + #{c < l : x_c == x_l}   (softmax_ce_kernel's tie rule: rank == 0 is its
+//   "correct"), loss = lse(x) - x_l in fp32.
+// A row is ignored when row >= nvalid[0] (a device scalar: one captured launch serves full and short
+// batches) or when its label is outside [0, C): the label is then never used as an index, the row
+// gets rank -1 / loss 0 and adds nothing. A counted row adds [loss, rank < 1, rank < k, 1] to
+// stats[0:4] (fp64; the block's rows are summed in LDS first, one atomic per statistic and block).
+// A NaN label logit: rank C (a miss at every k), loss NaN.
+// The two passes over the row are scalar loads (rows of an arbitrary C are not 16-byte aligned); the
+// second hits the cache. At B = 256 the whole matrix is 512 KB: the launch is latency, not bandwidth.
+// ----------------------------------------------------------------------------------------
+template <typename T>
+__global__ void ce_eval_kernel(const T* __restrict__ logits, const long long* __restrict__ labels, double* stats,
+                               int B, int C, int k, const int* __restrict__ nvalid, float* __restrict__ loss_out,
+                               int* __restrict__ rank_out) {
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wid;
+  __shared__ float s_loss[4];
+  __shared__ int s_flag[4];  // bit 0: counted, bit 1: rank < 1, bit 2: rank < k
+  float loss = 0.f;
+  int rank = -1, flag = 0;
+  if (row < B) {  // (wave-uniform)
+    const long long lab = labels[row];
+    const int nv = nvalid ? nvalid[0] : B;
+    if (row < nv && lab >= 0 && lab < (long long)C) {
+      const T* x = logits + (size_t)row * C;
+      const float xl = (float)x[lab];
+      const int l = (int)lab;
+      float mx = -INFINITY;
+      int cnt = 0;
+      for (int c = lane; c < C; c += 64) {
+        const float v = (float)x[c];
+        mx = fmaxf(mx, v);  // (a NaN element is skipped here and reaches the loss through the sum below)
+        cnt += (v > xl || (v == xl && c < l)) ? 1 : 0;
+      }
+      mx = wave_max(mx);
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, 64);
+      float se = 0.f;
+      for (int c = lane; c < C; c += 64) se += expf((float)x[c] - mx);
+      se = wave_sum(se);
+      loss = (mx + logf(se)) - xl;
+      rank = (xl != xl) ? C : cnt;
+      flag = 1 | ((rank < 1) ? 2 : 0) | ((rank < k) ? 4 : 0);
+    }
+    if (lane == 0) {
+      if (loss_out) loss_out[row] = loss;
+      if (rank_out) rank_out[row] = rank;
+    }
+  }
+  if (lane == 0) { s_loss[wid] = loss; s_flag[wid] = flag; }
+  __syncthreads();
+  if (threadIdx.x < 4) {
+    const int j = threadIdx.x;  // the statistic this thread owns
+    double v = 0.0;
+    for (int w = 0; w < 4; ++w) {
+      const int f = s_flag[w];
+      if (f & 1) v += (j == 0) ? (double)s_loss[w] : (j == 3) ? 1.0 : (double)((f >> j) & 1);
+    }
+    if (v != 0.0) atomicAdd(stats + j, v);  // (true for NaN too: a NaN loss reaches the sum)
+  }
+}
+
+// ----------------------------------------------------------------------------------------
 // Fused optimizers over the flat fp32 master buffer (+ optional bf16 compute copy).
 //   SGD (PyTorch semantics): d = g + wd*p; v = mom*v + (1-damp)*d (v = d at step 1);
 //                            d = nesterov ? d + mom*v : v; p -= lr*d
@@ -1292,6 +1380,13 @@ extern "C" int dbx_bn_eval_coeff(int C, const float* gamma, const float* beta, f
   hipLaunchKernelGGL(bn_eval_coeff_kernel, dim3((C + 255) / 256), dim3(256), 0, st, C, gamma, beta, eps, rm, rv, scale, shift);
   RET_LAST;
 }
+extern "C" int dbx_bn_eval_coeff_multi(const void* desc, int nbn, int max_c, hipStream_t st) {
+  if (nbn <= 0 || max_c <= 0) return 0;
+  if (!desc || nbn > 65535) return -1;
+  hipLaunchKernelGGL(bn_eval_coeff_multi_kernel, dim3(grid_for(max_c, 256, 64), nbn), dim3(256), 0, st,
+                     (const BnEvalDesc*)desc);
+  RET_LAST;
+}
 extern "C" int dbx_channel_stats(const bf16* y, long long M, int C, double* stats, int nshard, hipStream_t st) {
   if (C % 8 || C / 8 > 256) return -1;
   const int rpb = 256 / (C / 8);
@@ -1412,6 +1507,19 @@ extern "C" int dbx_softmax_ce(const void* logits, int is_bf16, const long long* 
   else
     hipLaunchKernelGGL(softmax_ce_kernel<float>, dim3(B), dim3(256), 0, st, (const float*)logits, labels,
                        (float*)dlogits, loss_out, stats, B, C, smoothing, gscale, labels2, lam);
+  RET_LAST;
+}
+extern "C" int dbx_ce_eval(const void* logits, int is_bf16, const long long* labels, double* stats, int B, int C, int k,
+                           const int* nvalid, float* loss_out, int* rank_out, hipStream_t st) {
+  if (B <= 0) return 0;
+  if (!logits || !labels || !stats || C < 1 || k < 1 || k > C) return -1;
+  const dim3 grid((B + 3) / 4);
+  if (is_bf16)
+    hipLaunchKernelGGL(ce_eval_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)logits, labels, stats, B, C, k, nvalid,
+                       loss_out, rank_out);
+  else
+    hipLaunchKernelGGL(ce_eval_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, labels, stats, B, C, k,
+                       nvalid, loss_out, rank_out);
   RET_LAST;
 }
 extern "C" int dbx_sgd(float* p, const float* g, float* v, bf16* p16, long long n, const float* hyper, float lr,

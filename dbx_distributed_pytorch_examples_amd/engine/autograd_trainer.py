@@ -245,15 +245,28 @@ class AutogradTrainer:
             self.count = 0
         return loss, corr
 
-    @torch.no_grad()
-    def eval_batch(self, x, y) -> Tuple[float, int]:
+    def _eval_logits(self, x, y):
         self.model.eval()
         x, y = x.to(self.dev), y.to(self.dev)
         if self.dev.type == "cuda" and x.dim() == 4:
             x = x.contiguous(memory_format=torch.channels_last)
         with torch.autocast(self.dev.type, dtype=torch.bfloat16, enabled=self.bf16):
             out = self.model((x, y)) if _is_composer(self.model) else self.model(x)
-        out = out.float()
+        return out.float(), y
+
+    @torch.no_grad()
+    def eval_stats(self, x, y, stats: torch.Tensor, topk: int = 5) -> None:
+        """Add the batch's [loss sum, top-1, top-k, count] to ``stats`` (fp64 [4] on the trainer's device)
+        by ``reference.ce_eval``: no host sync. ``topk`` is clipped to the class count (0 counts top-1).
+        A model that returns log-probabilities gets ``lse(x) - x_l = -x_l`` up to fp32 rounding."""
+        from ..ops import reference as R
+        out, y = self._eval_logits(x, y)
+        out = out.reshape(out.shape[0], -1).contiguous()
+        R.ce_eval(out, y.long(), stats, max(1, min(int(topk), out.shape[1])))
+
+    @torch.no_grad()
+    def eval_batch(self, x, y) -> Tuple[float, int]:
+        out, y = self._eval_logits(x, y)
         m = unwrap(self.model)
         if isinstance(m, _log_prob_types()):
             loss = F.nll_loss(out, y, reduction="sum")

@@ -14,6 +14,10 @@ capturing collectives inside a graph). The optimizer segment waits on the comm s
 Bucket sizing for xGMI: each segment range is split into chunks of ``bucket_cap_mb`` (default
 64 MiB: 8 GPUs x 7 point-to-point links want few, large messages; the 25 MiB NVSwitch-era
 default of torch DDP only adds launch latency here).
+
+Validation. ``eval_begin() / eval_step() / eval_end()``: weights and BN coefficients are prepared once
+per pass, each batch is one replay of a captured eval forward ending in the metrics kernel
+(``K.ce_eval``: loss, top-1, top-k on the device), and the pass ends with its one host read.
 """
 from __future__ import annotations
 
@@ -50,6 +54,16 @@ class OptimConfig:
     adapt_1d: bool = False       # LAMB: also decay and adapt BN affine parameters and biases (FusedLamb / apex)
     trust_min: float = 0.0       # LAMB trust-ratio clamp where adapted (0 = unbounded)
     trust_max: float = 0.0
+
+
+@dataclass
+class EvalResult:
+    """Sums of one evaluation pass (NativeTrainer.eval_end): divide by ``count`` for the means."""
+    loss_sum: float
+    top1: float   # rows whose label ranks first (ties: the lowest index wins, as in the training step)
+    topk: float   # rows whose label is among the k largest logits
+    count: int    # rows counted (labels outside [0, classes) are not)
+    k: int
 
 
 class NativeTrainer:
@@ -231,6 +245,15 @@ class NativeTrainer:
         self.ema = self.ema_bn = None
         if self.ema_decay > 0:
             self._alloc_ema()
+        # evaluation pass (eval_begin / eval_step / eval_end): its own fp64 [loss sum, top-1, top-k, count]
+        # and the batch's valid-row count as a device scalar, so one captured graph serves short batches
+        self.eval_stats = torch.zeros(4, device=device, dtype=torch.float64)
+        self.eval_nvalid = torch.zeros(1, device=device, dtype=torch.int32)
+        self.eval_graph: Optional[torch.cuda.CUDAGraph] = None
+        self._eval_on = False
+        self._eval_k = self._eval_graph_k = 0
+        self._eval_warm = 0
+        self._eval_n: Optional[int] = None  # what eval_nvalid holds
         self._build_phases()
         self.opt_ranges = self._optimizer_ranges()
         # broadcast initial parameters from rank 0 (DDP constructor semantics, M2)
@@ -265,6 +288,7 @@ class NativeTrainer:
             pairs += [(mean, bn.mod.running_mean), (var, bn.mod.running_var)]
             # what an evaluation from the average hands bn_eval_coeff (program._bn_fwd)
             bn.ema_eval = (self.ema[bn.off_w:bn.off_w + bn.C], self.ema[bn.off_b:bn.off_b + bn.C], mean, var)
+        p.bn_eval_table_ema = p.pack_bn_eval(ema=True)  # an evaluation pass from the average (eval_begin)
         self._ema_bn_desc = K.pack_ema_desc(pairs, dev)
         self._ema_bn_n, self._ema_bn_max = len(pairs), max(bn.C for bn in p.bns)
         self.ema_hyper = torch.zeros(1, device=dev)  # 1 - d_t (device-side, graph-safe)
@@ -740,6 +764,9 @@ class NativeTrainer:
         """One training step. ``images_u8`` [N,Hs,Ws,C] uint8, ``labels`` [N] int64, optional
         crop ``boxes`` [N,4] / ``flips`` [N] are copied into the program's static input buffers
         (pass None to reuse what is already there)."""
+        if self._eval_on:
+            # the BN scale / shift buffers the pass prepared once are the training forward's too
+            raise RuntimeError("step() inside an evaluation pass: call eval_end() first")
         p = self.prog
         p.training = True
         if images_u8 is not None:
@@ -813,6 +840,95 @@ class NativeTrainer:
             p.eval_ema = False
             p.training = True
         return out[:n]
+
+    # ----------------------------------------------------------------------------------
+    # Evaluation pass: eval_begin() prepares what does not change between the batches of one pass (the
+    # bf16 weights, every BN's eval coefficients: two launches), eval_step() runs augment + forward +
+    # ce_eval per batch -- one graph replay, no host sync -- and eval_end() does the pass's one host read.
+    @torch.no_grad()
+    def eval_begin(self, use_ema: Optional[bool] = None, topk: int = 5) -> None:
+        """Open an evaluation pass. ``use_ema`` as in :meth:`evaluate_batch`; the pass counts top-1 and
+        top-``min(topk, num_classes)``. No ``step()`` until :meth:`eval_end`."""
+        if self._eval_on:
+            raise RuntimeError("eval_begin() inside an evaluation pass: call eval_end() first")
+        p = self.prog
+        use_ema = self.ema is not None if use_ema is None else bool(use_ema)
+        if use_ema and self.ema is None:
+            raise ValueError("use_ema=True needs a trainer built with ema_decay > 0")
+        if int(topk) < 1:
+            raise ValueError(f"topk must be >= 1, got {topk}")
+        if self.comm_stream is not None:  # the last step's parameter all-gather (ZeRO)
+            torch.cuda.current_stream(self.dev).wait_stream(self.comm_stream)
+        p.prepare_weights(src=self.ema if use_ema else None)
+        p.bn_eval_coeffs(ema=use_ema)
+        self.eval_stats.zero_()
+        self._eval_k = min(int(topk), p.num_classes)
+        self._eval_on = True
+
+    def _eval_forward(self) -> None:
+        """Augment, stem, blocks, pool, fc, ce_eval: one chain on the current stream (the eval forward
+        forks nothing). Weights and BN coefficients are eval_begin's."""
+        p = self.prog
+        p.training = False
+        try:
+            p.load_input_u8(None)
+            p.forward(compute_grad=False, metrics=False, loss=False, bn_coeffs=False)
+            K.ce_eval(p.logits, p.labels, self.eval_stats, self._eval_k, nvalid=self.eval_nvalid)
+        finally:
+            p.training = True
+
+    def _capture_eval(self) -> None:
+        release_dead_graphs(self.dev)
+        s = torch.cuda.Stream(device=self.dev)
+        s.wait_stream(torch.cuda.current_stream(self.dev))
+        mode = "thread_local" if (dist.is_available() and dist.is_initialized()) else "global"  # (see _capture)
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.stream(s):
+            with torch.cuda.graph(g, stream=s, capture_error_mode=mode):
+                self._eval_forward()
+        torch.cuda.current_stream(self.dev).wait_stream(s)
+        torch.cuda.synchronize(self.dev)
+        self.eval_graph, self._eval_graph_k = g, self._eval_k
+
+    @torch.no_grad()
+    def eval_step(self, images_u8: torch.Tensor, labels: torch.Tensor, boxes: Optional[torch.Tensor] = None) -> None:
+        """One batch of ``n <= N`` samples: copied into the static input buffers, rows past ``n`` ignored
+        on the device. Never synchronises. With graphs, a trainer's first two calls run eagerly, the third
+        captures the eval forward and every later call -- of this pass or any later one, with or without
+        the average -- replays that one graph (k is a kernel argument: another top-k captures again)."""
+        if not self._eval_on:
+            raise RuntimeError("eval_step() without eval_begin()")
+        p = self.prog
+        n = int(images_u8.shape[0])
+        if not 0 < n <= p.N or labels.shape[0] != n:
+            raise ValueError(f"eval_step: {n} images and {labels.shape[0]} labels for a batch of {p.N}")
+        p.img_u8[:n].copy_(images_u8, non_blocking=True)
+        p.labels[:n].copy_(labels, non_blocking=True)
+        if boxes is not None:
+            p.boxes[:n].copy_(boxes, non_blocking=True)
+        if n != self._eval_n:
+            self.eval_nvalid.fill_(n)
+            self._eval_n = n
+        p.flip.zero_()
+        if not self.use_graphs:
+            self._eval_forward()
+            return
+        if self.eval_graph is None or self._eval_graph_k != self._eval_k:
+            if self._eval_warm < 2:
+                self._eval_warm += 1
+                self._eval_forward()
+                return
+            self.eval_graph = None
+            self._capture_eval()
+        self.eval_graph.replay()
+
+    def eval_end(self) -> "EvalResult":
+        """Close the pass and read its sums (the pass's one host read)."""
+        if not self._eval_on:
+            raise RuntimeError("eval_end() without eval_begin()")
+        self._eval_on = False
+        m = self.eval_stats.tolist()
+        return EvalResult(loss_sum=m[0], top1=m[1], topk=m[2], count=int(m[3]), k=self._eval_k)
 
     def _ema_maps(self):
         """(master address, the model's parameters by name, averaged buffer by running-statistic address)."""

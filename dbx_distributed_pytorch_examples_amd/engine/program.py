@@ -296,8 +296,11 @@ class ResNetProgram:
         self._alloc_activations()
         self.build_fins()
         self._pack_step_descs()
+        self.bn_eval_table = self.pack_bn_eval()
+        self.bn_eval_table_ema = None  # pack_bn_eval(ema=True), by a trainer that keeps a weight EMA
         self.training = True
         self.eval_ema = False  # evaluate from the trainer's weight EMA (NativeTrainer.evaluate_batch)
+        self._skip_eval_coeff = False  # forward(bn_coeffs=False): the eval coefficients are in place already
 
     # ----------------------------------------------------------------------------------
     # construction
@@ -690,6 +693,22 @@ class ResNetProgram:
                 if b.bns[-1].fin_f.desc is not None and b.ds_bn.fin_f.desc is not None:
                     b.bns[-1].fin_f.pair_ptr(b.ds_bn.fin_f)
 
+    def pack_bn_eval(self, ema: bool = False):
+        """The K.bn_eval_coeff_multi table of every BN's eval coefficients (scale / shift from the running
+        statistics) -- from the module's parameters and buffers, or (``ema``) from the trainer's averaged
+        views ``bn.ema_eval``. Raw pointers, like the finalize descriptors: rebuild with them."""
+        rows = []
+        for bn in self.bns:
+            gamma, beta, rmean, rvar = bn.ema_eval if ema else (bn.gamma, bn.beta, bn.mod.running_mean,
+                                                                bn.mod.running_var)
+            rows.append((gamma, beta, bn.mod.eps, rmean, rvar, bn.scale, bn.shift))
+        return K.pack_bn_eval_desc(rows, self.dev)
+
+    def bn_eval_coeffs(self, ema: bool = False) -> None:
+        """Every BN's eval-mode scale / shift in one launch (what forward(bn_coeffs=False) relies on)."""
+        table = self.bn_eval_table_ema if ema else self.bn_eval_table
+        K.bn_eval_coeff_multi(*table)
+
     def _ff(self, bn):
         """The forward finalize descriptor to hand the conv producing ``bn``'s statistics (training)."""
         return bn.fin_f if self.training and self.fuse_fin else None
@@ -753,6 +772,8 @@ class ResNetProgram:
             mom = mod.momentum if mod.momentum is not None else 0.1
             K.bn_finalize(bn.stats, count, bn.gamma, bn.beta, mod.eps, mom if mod.track_running_stats else 0.0,
                           mod.running_mean, mod.running_var, bn.scale, bn.shift, bn.mean, bn.invstd)
+        elif self._skip_eval_coeff:  # computed once for the whole pass (bn_eval_coeffs)
+            return
         elif self.eval_ema:  # the trainer's averaged affine parameters and running statistics
             gamma, beta, rmean, rvar = bn.ema_eval
             K.bn_eval_coeff(gamma, beta, mod.eps, rmean, rvar, bn.scale, bn.shift)
@@ -760,11 +781,15 @@ class ResNetProgram:
             K.bn_eval_coeff(bn.gamma, bn.beta, mod.eps, mod.running_mean, mod.running_var, bn.scale, bn.shift)
 
     def forward(self, smoothing: float = 0.0, compute_grad: bool = True, grad_scale: float = 1.0,
-                metrics: bool = True, features_only: bool = False):
+                metrics: bool = True, features_only: bool = False, loss: bool = True, bn_coeffs: bool = True):
         """Full forward incl. loss. Assumes x4 / labels filled and prepare_weights() done.
         ``features_only``: stop after global average pooling and return ``self.pooled`` [N, C]
-        (frozen-backbone feature extraction; the fc / loss are left to the caller)."""
+        (frozen-backbone feature extraction; the fc / loss are left to the caller).
+        ``loss=False``: stop after the fc (no softmax-CE launch; the caller takes ``self.logits``).
+        ``bn_coeffs=False`` (eval mode only): no per-BN coefficient launches -- the caller ran
+        ``bn_eval_coeffs()`` after the last change of the weights or running statistics."""
         tr = self.training
+        self._skip_eval_coeff = not bn_coeffs and not tr
         if tr and not self._stats_zeroed:
             self.stats_region.zero_()
         self._stats_zeroed = False
@@ -858,6 +883,8 @@ class ResNetProgram:
             return self.pooled
         F, Cn = self.feat_c, self.num_classes
         K.small_gemm(self.pooled, self.fc_w16, self.logits, M=N, N=Cn, K=F, bias=self.fc_b16, ws=self.head_ws)
+        if not loss:
+            return self.logits
         mix = self.cutmix and self.training
         K.softmax_ce(self.logits, self.labels, self.dlogits if compute_grad else None, None,
                      self.metrics if metrics else None, smoothing=smoothing, grad_scale=grad_scale,

@@ -982,6 +982,47 @@ def bn_eval_coeff(gamma, beta, eps, running_mean, running_var, scale, shift):
                       running_var.data_ptr(), scale.data_ptr(), shift.data_ptr(), stream_ptr())
 
 
+def pack_bn_eval_desc(entries, device) -> torch.Tensor:
+    """Descriptor table of one :func:`bn_eval_coeff_multi` launch (csrc/nn_ops.hip BnEvalDesc: the
+    addresses of gamma, beta, running mean, running var, scale, shift, then C and eps = 56 bytes per
+    entry) from ``(gamma, beta, eps, running_mean, running_var, scale, shift)`` tuples, the arguments of
+    :func:`bn_eval_coeff` (gamma / beta may be None). Returns ``(table, entries, widest C)``, what
+    :func:`bn_eval_coeff_multi` takes. The table holds raw addresses: rebuild it if a tensor it names
+    is reallocated."""
+    import numpy as np
+    want = torch.device(device)
+    rows = np.zeros(len(entries), dtype=_ref.bn_eval_desc_dtype())
+    for i, (gamma, beta, eps, rm, rv, scale, shift) in enumerate(entries):
+        n = scale.numel()
+        for t, nm in ((gamma, "gamma"), (beta, "beta"), (rm, "running_mean"), (rv, "running_var"), (scale, "scale"),
+                      (shift, "shift")):
+            if t is None and nm in ("gamma", "beta"):
+                continue
+            if t.dtype != torch.float32:
+                raise TypeError(f"pack_bn_eval_desc: entry {i} {nm}: expected torch.float32, got {t.dtype}")
+            same_dev = t.device.type == want.type and (want.index is None or t.device.index == want.index)
+            if not t.is_contiguous() or not same_dev:
+                raise ValueError(f"pack_bn_eval_desc: entry {i} {nm}: must be contiguous and on {device}")
+            if t.numel() != n:
+                raise ValueError(f"pack_bn_eval_desc: entry {i} {nm}: {t.numel()} elements, scale has {n}")
+        rows[i] = ([_p(gamma), _p(beta), rm.data_ptr(), rv.data_ptr(), scale.data_ptr(), shift.data_ptr()], n, eps)
+    table = torch.from_numpy(rows.view(np.uint8).copy()).to(device)
+    return table, len(entries), max((int(r["C"]) for r in rows), default=0)
+
+
+@_dispatch
+def bn_eval_coeff_multi(desc, nbn, max_c):
+    """:func:`bn_eval_coeff` over every entry of a :func:`pack_bn_eval_desc` table in ONE launch (grid =
+    (blocks, nbn)): all the BatchNorms of a model before an evaluation pass. The same expression per
+    element, the same bits as one :func:`bn_eval_coeff` per entry. ``max_c``: the widest entry."""
+    if desc.dtype != torch.uint8:
+        raise TypeError(f"desc: expected torch.uint8, got {desc.dtype}")
+    if not desc.is_contiguous() or desc.numel() != _ref.BN_EVAL_DESC_BYTES * int(nbn):
+        raise ValueError(f"desc: expected a contiguous [{nbn}, {_ref.BN_EVAL_DESC_BYTES}] byte table, got shape "
+                         f"{tuple(desc.shape)}")
+    C().bn_eval_coeff_multi(desc.data_ptr(), int(nbn), int(max_c), stream_ptr())
+
+
 @_dispatch
 def channel_stats(y, stats):
     Cc = y.shape[-1]
@@ -1220,6 +1261,20 @@ def softmax_ce(logits, labels, dlogits=None, loss_out=None, stats=None, smoothin
     C().softmax_ce(logits.data_ptr(), int(logits.dtype == torch.bfloat16), labels.data_ptr(), _p(dlogits),
                    _p(loss_out), _p(stats), B, Cc, float(smoothing), float(grad_scale), _p(labels2), _p(lam),
                    stream_ptr())
+
+
+@_dispatch
+def ce_eval(logits, labels, stats, k, nvalid=None, loss_out=None, rank_out=None):
+    """Evaluation metrics without a gradient: per row the loss ``lse(x) - x_l`` (fp32, no smoothing) and
+    the label's rank ``#{x_c > x_l} + #{c < l : x_c == x_l}``; ``stats`` (fp64 [4], accumulated, never
+    zeroed here) ``+= [loss, rank < 1, rank < k, 1]`` per counted row. Rows at or past ``nvalid[0]``
+    (int32 [1] device tensor, read by the kernel: one captured launch serves full and short batches)
+    and rows whose label is outside [0, C) are ignored (``rank_out`` -1, ``loss_out`` 0, the label never
+    used as an index). ``rank == 0`` is :func:`softmax_ce`'s "correct". See ``reference.ce_eval``."""
+    B, Cc = _ref.check_ce_eval(logits, labels, stats, k, nvalid, loss_out, rank_out)
+    _chk(logits, logits.dtype, "logits")
+    C().ce_eval(logits.data_ptr(), int(logits.dtype == torch.bfloat16), labels.data_ptr(), stats.data_ptr(), B, Cc,
+                int(k), _p(nvalid), _p(loss_out), _p(rank_out), stream_ptr())
 
 
 def dropout_threshold(p_drop: float) -> Tuple[int, float]:

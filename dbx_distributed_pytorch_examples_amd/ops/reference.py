@@ -201,6 +201,31 @@ def bn_eval_coeff(gamma, beta, eps, running_mean, running_var, scale, shift):
     shift.copy_(b - running_mean * g * inv)
 
 
+BN_EVAL_DESC_BYTES = 56  # csrc/nn_ops.hip BnEvalDesc: six addresses (int64), C (int32), eps (fp32)
+
+
+def bn_eval_desc_dtype():
+    import numpy as np
+    return np.dtype([("ptr", np.int64, (6,)), ("C", np.int32), ("eps", np.float32)])
+
+
+def bn_eval_coeff_multi(desc, nbn, max_c):
+    """The table holds host addresses here: each entry is viewed in place and run through bn_eval_coeff."""
+    import ctypes
+    if desc.dtype != torch.uint8 or desc.numel() != BN_EVAL_DESC_BYTES * int(nbn):
+        raise ValueError("bn_eval_coeff_multi: expected a uint8 [nbn, 56] table")
+
+    def view(addr, n):
+        return torch.frombuffer((ctypes.c_float * n).from_address(addr), dtype=torch.float32) if addr else None
+
+    for row in desc.numpy().view(bn_eval_desc_dtype()):
+        n = int(row["C"])
+        if n <= 0:
+            continue
+        gamma, beta, rm, rv, scale, shift = (view(int(a), n) for a in row["ptr"])
+        bn_eval_coeff(gamma, beta, float(row["eps"]), rm, rv, scale, shift)
+
+
 def channel_stats(y, stats):
     check_channels(y.shape[-1])
     _add_stats(stats, y)
@@ -395,6 +420,57 @@ def softmax_ce(logits, labels, dlogits=None, loss_out=None, stats=None, smoothin
         if labels2 is not None:
             t.scatter_add_(1, labels2[:, None], torch.full((B, 1), (1 - smoothing) * (1 - lm), device=p.device))
         dlogits.copy_(((p - t) * grad_scale / B).to(dlogits.dtype))
+
+
+def check_ce_eval(logits, labels, stats, k, nvalid=None, loss_out=None, rank_out=None):
+    """Host-side argument checks of :func:`ce_eval`, shared with the kernel front-end; returns (B, C)."""
+    if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.bfloat16) or not logits.is_contiguous():
+        raise TypeError("ce_eval: logits must be a contiguous [B, C] fp32 / bf16 matrix")
+    B, C = logits.shape
+    if isinstance(k, bool) or not isinstance(k, int):
+        raise ValueError(f"ce_eval: k must be an int, got {k!r}")
+    if not 1 <= k <= C:
+        raise ValueError(f"ce_eval: k must be in [1, {C}], got {k}")
+    for t, dt, n, nm in ((labels, torch.int64, B, "labels"), (stats, torch.float64, 4, "stats"),
+                         (nvalid, torch.int32, 1, "nvalid"), (loss_out, torch.float32, B, "loss_out"),
+                         (rank_out, torch.int32, B, "rank_out")):
+        if t is None and nm not in ("labels", "stats"):
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise TypeError(f"ce_eval: {nm}: expected a {dt} tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"ce_eval: {nm}: expected {n} contiguous elements, got shape {tuple(t.shape)}")
+        if t.device != logits.device:
+            raise ValueError(f"ce_eval: {nm} is on {t.device}, logits on {logits.device}")
+    return B, C
+
+
+def ce_eval(logits, labels, stats, k, nvalid=None, loss_out=None, rank_out=None):
+    """Evaluation metrics of a logits matrix, on any device and without a host sync: for a row with
+    label l, ``rank = #{c : x_c > x_l} + #{c < l : x_c == x_l}`` (values compared in fp32; among equal
+    values the lowest index wins, so ``rank == 0`` is :func:`softmax_ce`'s "correct") and
+    ``loss = lse(x) - x_l`` in fp32. Rows at or past ``nvalid[0]`` (int32 device scalar) and rows whose
+    label is outside [0, C) are ignored: rank -1, loss 0, nothing added, the label never used as an
+    index. Every other row adds ``[loss, rank < 1, rank < k, 1]`` to ``stats`` (fp64 [4], accumulated,
+    never zeroed here); a NaN label logit gives rank C (a miss at every k) and a NaN loss."""
+    B, C = check_ce_eval(logits, labels, stats, k, nvalid, loss_out, rank_out)
+    dev = logits.device
+    lf = logits.float()
+    valid = (labels >= 0) & (labels < C)
+    if nvalid is not None:
+        valid &= torch.arange(B, device=dev) < nvalid.reshape(-1)[0]
+    lab = torch.where(valid, labels, torch.zeros_like(labels))[:, None]
+    xl = lf.gather(1, lab)
+    ahead = (lf > xl) | ((lf == xl) & (torch.arange(C, device=dev)[None, :] < lab))
+    rank = torch.where(xl.squeeze(1).isnan(), torch.full_like(labels, C), ahead.sum(1))
+    loss = torch.logsumexp(lf, 1) - xl.squeeze(1)
+    loss = torch.where(valid, loss, torch.zeros_like(loss))
+    stats += torch.stack([loss.double().sum(), (valid & (rank < 1)).sum().double(),
+                          (valid & (rank < k)).sum().double(), valid.sum().double()])
+    if loss_out is not None:
+        loss_out.copy_(loss.view_as(loss_out))
+    if rank_out is not None:
+        rank_out.copy_(torch.where(valid, rank, torch.full_like(rank, -1)).view_as(rank_out))
 
 
 def sgd_step(p, g, v, p16=None, *, lr, momentum, dampening=0.0, weight_decay=0.0, nesterov=False, first=False,

@@ -13,6 +13,9 @@ logging, checkpoints. This module implements that loop once:
   ``learning_rate``); no per-step ``.item()`` host syncs (the reference does two per step);
 * evaluation: sharded over ranks and reduced (the reference evaluates on rank 0 only, or on
   every rank redundantly in 03a), deterministic transforms (no train-time augmentation on val);
+  loss, top-1 and top-k (``val_top{k}_accuracy``, ``eval_topk``) are summed on the device by
+  ``ce_eval`` and read once per pass -- on the native engine each batch is one replay of a captured
+  eval forward (``eval_graph``);
 * checkpoints: ``checkpoint-{epoch}.pth.tar`` (rank 0) with full resume state; ``resume="latest"``
   continues from the newest one (used by launcher restarts);
 * early stopping on validation loss with ``patience`` (`02_deepspeed/02_tiny_imagenet_deepspeed_resnet.py:289-297`,
@@ -144,6 +147,7 @@ class _Native:
                                     cutmix_alpha=cfg.data.cutmix_alpha, seed=cfg.seed,
                                     grad_accum=cfg.grad_accum, ema_decay=cfg.ema_decay, ema_warmup=cfg.ema_warmup)
         self.ema_eval = bool(cfg.ema_eval)
+        self.eval_topk, self.eval_graph = _eval_topk(cfg), bool(cfg.eval_graph)
         if not cfg.data.augment:
             aug = AugmentSpec()
         elif (h, w) == (s, s) and s <= 64:
@@ -185,25 +189,47 @@ class _Native:
         return self.tr.read_metrics()
 
     @torch.no_grad()
-    def eval_dataset(self, ds) -> Tuple[float, float, int]:
+    def eval_dataset(self, ds) -> Tuple[float, float, float, int]:
+        """(loss sum, top-1 count, top-k count, samples) of this rank's shard of ``ds``."""
         import torch.nn.functional as F
-        from ..data.loader import NativeImageLoader, sample_boxes
+        from ..data.loader import NativeImageLoader
+        from ..ops import kernels as K
+        tr = self.tr
         sampler = ShardSampler(ds, shuffle=False, drop_last=False) if not hasattr(ds, "epoch_indices") else None
         h, w, c = _sample_hw(ds)
-        ld = NativeImageLoader(ds, self.batch, (h, w), self.tr.dev, channels=c, augment=self.eval_spec,
-                               out_hw=(self.tr.prog.H, self.tr.prog.W), drop_last=False,
+        ld = NativeImageLoader(ds, self.batch, (h, w), tr.dev, channels=c, augment=self.eval_spec,
+                               out_hw=(tr.prog.H, tr.prog.W), drop_last=False,
                                indices_fn=(lambda e: sampler.indices().numpy()) if sampler else None, prefetch=1)
+        has_ema = getattr(tr, "ema", None) is not None  # cfg.ema_eval: validate the averaged weights
+        k = self.eval_topk  # (0: no top-k count; clipped to the class count where it is used)
+        if self.eval_graph and hasattr(tr, "eval_begin"):
+            # one prepared pass: a graph replay per batch, metrics on the device, one host read
+            tr.eval_begin(use_ema=self.ema_eval if has_ema else None, topk=max(k, 1))  # (clips k itself)
+            try:
+                for img, lab, boxes, _ in ld:
+                    tr.eval_step(img, lab, boxes)
+            finally:
+                r = tr.eval_end()
+            return r.loss_sum, r.top1, (r.topk if k else 0.0), r.count
+        stats = torch.zeros(4, device=tr.dev, dtype=torch.float64)  # K.ce_eval's sums, read once
+        frozen = not hasattr(tr, "eval_begin")  # frozen backbone: every metric from the device buffer
         loss, corr, n = 0.0, 0.0, 0
-        seen = set()
         for img, lab, boxes, _ in ld:
-            if getattr(self.tr, "ema", None) is not None:  # cfg.ema_eval: validate the averaged weights
-                logits = self.tr.evaluate_batch(img, lab, boxes, use_ema=self.ema_eval).float()
+            if has_ema:
+                logits = tr.evaluate_batch(img, lab, boxes, use_ema=self.ema_eval)
             else:
-                logits = self.tr.evaluate_batch(img, lab, boxes).float()
-            loss += F.cross_entropy(logits, lab, reduction="sum").item()
-            corr += (logits.argmax(1) == lab).sum().item()
-            n += lab.shape[0]
-        return loss, corr, n
+                logits = tr.evaluate_batch(img, lab, boxes)
+            if frozen or k:
+                K.ce_eval(logits.contiguous(), lab, stats, max(1, min(k, logits.shape[1])))
+            if not frozen:  # eval_graph off: the host path (torch CE and argmax on the fp32 logits)
+                logits = logits.float()
+                loss += F.cross_entropy(logits, lab, reduction="sum").item()
+                corr += (logits.argmax(1) == lab).sum().item()
+                n += lab.shape[0]
+        s = stats.tolist()
+        if frozen:
+            return s[0], s[1], (s[2] if k else 0.0), int(s[3])
+        return loss, corr, (s[2] if k else 0.0), n
 
     @property
     def model(self):
@@ -223,6 +249,7 @@ class _Autograd:
                                                 num_workers=cfg.data.num_workers if dev.type == "cuda" else 0,
                                                 pin=dev.type == "cuda")
         self.batch = cfg.batch_size
+        self.eval_topk = _eval_topk(cfg)
 
     def epoch_batches(self, epoch):
         if self.sampler is not None:
@@ -248,14 +275,14 @@ class _Autograd:
         return self.tr.read_metrics()
 
     def eval_dataset(self, ds):
+        """(loss sum, top-1 count, top-k count, samples): ``reference.ce_eval`` on every batch's logits into
+        one device buffer, read once."""
         loader, _ = make_loader(ds, self.batch, False, 0)
-        loss, corr, n = 0.0, 0, 0
+        stats = torch.zeros(4, device=self.tr.dev, dtype=torch.float64)
         for x, y in loader:
-            l, c = self.tr.eval_batch(x, y)
-            loss += l
-            corr += c
-            n += y.shape[0]
-        return loss, float(corr), n
+            self.tr.eval_stats(x, y, stats, self.eval_topk)
+        s = stats.tolist()
+        return s[0], s[1], (s[2] if self.eval_topk else 0.0), int(s[3])
 
     @property
     def model(self):
@@ -295,10 +322,22 @@ def _apply_env_overrides(cfg: TrainConfig) -> TrainConfig:
     return cfg
 
 
+def _eval_topk(cfg: TrainConfig) -> int:
+    if cfg.eval_topk < 0:
+        raise ValueError(f"eval_topk must be >= 0 (0 = off), got {cfg.eval_topk}")
+    return int(cfg.eval_topk)
+
+
 def evaluate(runner, dataset) -> Dict[str, float]:
-    loss, corr, n = runner.eval_dataset(dataset)
-    loss, corr, n = ddist.all_reduce_sum([loss, corr, float(n)])
-    return {"val_loss": loss / max(1.0, n), "val_accuracy": corr / max(1.0, n), "val_samples": n}
+    """``val_loss``, ``val_accuracy``, ``val_top{k}_accuracy`` (k = ``eval_topk``, unless 0; a model with
+    fewer than k classes counts top-``num_classes``) and ``val_samples``: one packed all-reduce."""
+    loss, corr, topk, n = runner.eval_dataset(dataset)
+    loss, corr, topk, n = ddist.all_reduce_sum([loss, corr, topk, float(n)])
+    out = {"val_loss": loss / max(1.0, n), "val_accuracy": corr / max(1.0, n), "val_samples": n}
+    k = getattr(runner, "eval_topk", 0)
+    if k:
+        out[f"val_top{k}_accuracy"] = topk / max(1.0, n)
+    return out
 
 
 def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = None,
