@@ -15,7 +15,9 @@ from __future__ import annotations
 
 import copy
 import dataclasses
+import fnmatch
 import json
+import math
 import os
 import re
 from dataclasses import dataclass, field
@@ -62,6 +64,10 @@ class OptimizerConfig:
     adapt_1d: bool = False             # LAMB: also decay and adapt BN affine parameters and biases
     trust_min: float = 0.0             # LAMB trust-ratio clamp where adapted (0 = unbounded)
     trust_max: float = 0.0
+    # parameter groups (sgd | adam | adamw; see resolve_param_groups)
+    groups: list = field(default_factory=list)  # [{match: "layer4.*" | [patterns], weight_decay: float?, lr_mult: float?}, ...]
+    norm_weight_decay: float = -1.0    # < 0: use weight_decay. Applies to every parameter of a normalisation layer
+    bias_weight_decay: float = -1.0    # < 0: use weight_decay. Applies to biases of all other layers (fc.bias)
 
 
 @dataclass
@@ -167,6 +173,12 @@ def _coerce(cur: Any, val: Any) -> Any:
         if isinstance(val, str):
             val = [float(x) for x in val.strip("()[]").split(",")]
         return tuple(type(c)(v) for c, v in zip(cur, val))
+    if isinstance(cur, list):
+        if isinstance(val, str):  # a CLI override: optim.groups='[{"match": "fc.*", "lr_mult": 10}]'
+            val = json.loads(val)
+        if not isinstance(val, (list, tuple)):
+            raise ValueError(f"expected a list, got {val!r}")
+        return list(val)
     return val
 
 
@@ -229,6 +241,92 @@ def load_local_config(path: str = "../local_config.yaml") -> LocalConfig:
 
 def to_dict(cfg: Any) -> Dict[str, Any]:
     return dataclasses.asdict(cfg)
+
+
+# ----------------------------------------------------------------------------------------
+_GROUP_KEYS = ("match", "weight_decay", "lr_mult")
+
+
+def has_param_groups(optim: Any) -> bool:
+    """Whether ``optim`` sets any per-parameter-group field (``groups`` or one of the two shorthands)."""
+    return bool(getattr(optim, "groups", None)) or float(getattr(optim, "norm_weight_decay", -1.0)) >= 0 \
+        or float(getattr(optim, "bias_weight_decay", -1.0)) >= 0 \
+        or any(math.isnan(float(getattr(optim, k, -1.0))) for k in ("norm_weight_decay", "bias_weight_decay"))
+
+
+def reject_param_groups(optim: Any, who: str) -> None:
+    """For the engines and optimizers that keep one weight decay and one lr: refuse, never ignore."""
+    if has_param_groups(optim):
+        raise ValueError(f"{who} does not support parameter groups (optim.groups / norm_weight_decay / "
+                         f"bias_weight_decay); they work with sgd, adam and adamw on the native engine at "
+                         f"zero.stage 0 and on the autograd engine")
+
+
+def _group_patterns(g: Dict[str, Any], i: int) -> List[str]:
+    if not isinstance(g, dict):
+        raise ValueError(f"optim.groups[{i}]: expected a mapping with 'match', got {g!r}")
+    bad = [k for k in g if k not in _GROUP_KEYS]
+    if bad:
+        raise KeyError(f"unknown config key {bad[0]!r} for optim.groups[{i}] (known: {', '.join(_GROUP_KEYS)})")
+    m = g.get("match")
+    pats = [m] if isinstance(m, str) else list(m or [])
+    if not pats or not all(isinstance(x, str) for x in pats):
+        raise ValueError(f"optim.groups[{i}]: 'match' must be a pattern or a list of patterns")
+    return pats
+
+
+def _group_value(v: Any, what: str) -> float:
+    v = float(v)
+    if not math.isfinite(v) or v < 0:
+        raise ValueError(f"{what} must be finite and >= 0, got {v}")
+    return v
+
+
+def resolve_param_groups(named_kinds: Sequence[Tuple[str, str]], optim: Any) -> Optional[List[Tuple[float, float]]]:
+    """Per-parameter ``(weight_decay, lr_mult)`` for ``[(name, kind)]`` (``kind``: weight | norm | bias; names
+    as ``model.named_parameters()`` gives them), or None when ``optim`` sets no group field at all.
+
+    ``optim.groups`` are tried in order against the name (``fnmatch`` patterns) and the first match wins;
+    its ``weight_decay`` is absolute, its ``lr_mult`` multiplies the scheduled learning rate. A key the
+    matching group leaves out (and every key of an unmatched parameter) falls through to
+    ``norm_weight_decay`` (kind norm) / ``bias_weight_decay`` (kind bias) when >= 0, then to
+    ``weight_decay`` and an ``lr_mult`` of 1."""
+    if not has_param_groups(optim):
+        return None
+    base = float(optim.weight_decay)
+    short = {}
+    for kind, key in (("norm", "norm_weight_decay"), ("bias", "bias_weight_decay")):
+        v = float(getattr(optim, key, -1.0))
+        if math.isnan(v) or v == math.inf:
+            raise ValueError(f"optim.{key} must be finite, got {v}")
+        if v >= 0:
+            short[kind] = v
+    groups = []
+    for i, g in enumerate(getattr(optim, "groups", None) or []):
+        pats = _group_patterns(g, i)
+        wd = _group_value(g["weight_decay"], f"optim.groups[{i}].weight_decay") if g.get("weight_decay") is not None else None
+        lm = _group_value(g["lr_mult"], f"optim.groups[{i}].lr_mult") if g.get("lr_mult") is not None else None
+        if not any(fnmatch.fnmatchcase(name, pat) for name, _ in named_kinds for pat in pats):
+            raise ValueError(f"optim.groups[{i}] (match={g['match']!r}) matches no parameter")
+        groups.append((pats, wd, lm))
+    out = []
+    for name, kind in named_kinds:
+        if kind not in ("weight", "norm", "bias"):
+            raise ValueError(f"parameter {name!r}: unknown kind {kind!r}")
+        wd = lm = None
+        for pats, gwd, glm in groups:
+            if any(fnmatch.fnmatchcase(name, pat) for pat in pats):
+                wd, lm = gwd, glm
+                break
+        if wd is None:
+            wd = short.get(kind, base)
+        out.append((float(wd), 1.0 if lm is None else float(lm)))
+    return out
+
+
+def distinct_param_groups(values: Sequence[Tuple[float, float]]) -> List[Tuple[float, float]]:
+    """The distinct ``(weight_decay, lr_mult)`` pairs in first-seen order."""
+    return list(dict.fromkeys(values))
 
 
 # ----------------------------------------------------------------------------------------

@@ -63,6 +63,15 @@ int dbx_sgd_ema(float*, const float*, float*, bf16*, long long, const float*, fl
                 const float*, float, float*, const float*, float, hipStream_t);
 int dbx_adam_ema(float*, const float*, float*, float*, bf16*, long long, const float*, float, float, float, float, float,
                  int, float, float, const float*, float, float*, const float*, float, hipStream_t);
+int dbx_sgd_groups(float*, const float*, float*, bf16*, long long, const float*, float, float, float, int, int,
+                   const float*, float, const int*, int, long long, hipStream_t);
+int dbx_sgd_groups_ema(float*, const float*, float*, bf16*, long long, const float*, float, float, float, int, int,
+                       const float*, float, const int*, int, long long, float*, const float*, float, hipStream_t);
+int dbx_adam_groups(float*, const float*, float*, float*, bf16*, long long, const float*, float, float, float, float,
+                    int, float, float, const float*, float, const int*, int, long long, hipStream_t);
+int dbx_adam_groups_ema(float*, const float*, float*, float*, bf16*, long long, const float*, float, float, float,
+                        float, int, float, float, const float*, float, const int*, int, long long, float*,
+                        const float*, float, hipStream_t);
 int dbx_ema_update(float*, const float*, long long, const float*, float, hipStream_t);
 int dbx_ema_update_multi(const void*, int, long long, const float*, float, hipStream_t);
 int dbx_sumsq(const float*, long long, double*, hipStream_t);
@@ -370,6 +379,41 @@ PYBIND11_MODULE(_C, m) {
                        P<const float*>(hyper), lr, b1, b2, eps, wd, decoupled, bc1, bc2, P<const float*>(gsp), gs,
                        P<float*>(ema), P<const float*>(omd_ptr), omd, S(st)),
           "adam_ema");
+  });
+  m.def("sgd_groups", [](uintptr_t p, uintptr_t g, uintptr_t v, uintptr_t p16, long long n, uintptr_t hyper, float lr,
+                         float mom, float damp, int nesterov, int first, uintptr_t gsp, float gs, uintptr_t tab,
+                         int nruns, long long run_base, uintptr_t st) {
+    check(dbx_sgd_groups(P<float*>(p), P<const float*>(g), P<float*>(v), P<bf16*>(p16), n, P<const float*>(hyper), lr,
+                         mom, damp, nesterov, first, P<const float*>(gsp), gs, P<const int*>(tab), nruns, run_base,
+                         S(st)),
+          "sgd_groups");
+  });
+  m.def("sgd_groups_ema", [](uintptr_t p, uintptr_t g, uintptr_t v, uintptr_t p16, long long n, uintptr_t hyper,
+                             float lr, float mom, float damp, int nesterov, int first, uintptr_t gsp, float gs,
+                             uintptr_t tab, int nruns, long long run_base, uintptr_t ema, uintptr_t omd_ptr, float omd,
+                             uintptr_t st) {
+    check(dbx_sgd_groups_ema(P<float*>(p), P<const float*>(g), P<float*>(v), P<bf16*>(p16), n, P<const float*>(hyper),
+                             lr, mom, damp, nesterov, first, P<const float*>(gsp), gs, P<const int*>(tab), nruns,
+                             run_base, P<float*>(ema), P<const float*>(omd_ptr), omd, S(st)),
+          "sgd_groups_ema");
+  });
+  m.def("adam_groups", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t p16, long long n,
+                          uintptr_t hyper, float lr, float b1, float b2, float eps, int decoupled, float bc1, float bc2,
+                          uintptr_t gsp, float gs, uintptr_t tab, int nruns, long long run_base, uintptr_t st) {
+    check(dbx_adam_groups(P<float*>(p), P<const float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(p16), n,
+                          P<const float*>(hyper), lr, b1, b2, eps, decoupled, bc1, bc2, P<const float*>(gsp), gs,
+                          P<const int*>(tab), nruns, run_base, S(st)),
+          "adam_groups");
+  });
+  m.def("adam_groups_ema", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t p16, long long n,
+                              uintptr_t hyper, float lr, float b1, float b2, float eps, int decoupled, float bc1,
+                              float bc2, uintptr_t gsp, float gs, uintptr_t tab, int nruns, long long run_base,
+                              uintptr_t ema, uintptr_t omd_ptr, float omd, uintptr_t st) {
+    check(dbx_adam_groups_ema(P<float*>(p), P<const float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(p16), n,
+                              P<const float*>(hyper), lr, b1, b2, eps, decoupled, bc1, bc2, P<const float*>(gsp), gs,
+                              P<const int*>(tab), nruns, run_base, P<float*>(ema), P<const float*>(omd_ptr), omd,
+                              S(st)),
+          "adam_groups_ema");
   });
   m.def("ema_update", [](uintptr_t e, uintptr_t p, long long n, uintptr_t omd_ptr, float omd, uintptr_t st) {
     check(dbx_ema_update(P<float*>(e), P<const float*>(p), n, P<const float*>(omd_ptr), omd, S(st)), "ema_update");

@@ -812,13 +812,56 @@ __device__ __forceinline__ float ema_lerp(float e, float p, float omd) { return 
 template <bool EMA> struct EmaArgs { float* e; const float* omd_ptr; float omd; };
 template <> struct EmaArgs<false> {};
 
-template <bool EMA>
+// Parameter groups (compile-time variant GROUPS = true): weight decay and an LR multiplier per RUN of the
+// flat buffer. tab (device int32, ops/kernels.py pack_opt_runs) = start[nruns + 1] | wd[nruns] | lr_mult[nruns]
+// (the last two fp32 bits): run r covers flat indices [start[r], start[r + 1]), start[0] = 0, strictly
+// increasing multiples of 4, so a 16-byte vector at a flat index that is a multiple of 4 lies in ONE run.
+// run_base = the flat index of p[0] (a multiple of 4): a slice of the master uses the whole buffer's table.
+// Every block copies start / wd / lr_mult into LDS once (12 KiB at the limit) and a lane finds its vector's
+// run by a binary search there (neighbouring lanes read the same words: broadcasts); the per-element math is
+// the plain kernel's with wd -> wd[r] and lr -> lr * lr_mult[r]. No HBM traffic per element is added. The host
+// validates the table; the run index is clamped all the same: a bad table gives wrong numbers, never a
+// read outside the LDS arrays.
+constexpr int kOptMaxRuns = 1024;  // ops/kernels.py OPT_MAX_RUNS
+template <bool GROUPS> struct GroupArgs { const int* tab; int nruns; int run_base; };
+template <> struct GroupArgs<false> {};
+struct OptRunsLds { int start[kOptMaxRuns]; float wd[kOptMaxRuns]; float lm[kOptMaxRuns]; };
+
+__device__ __forceinline__ int opt_runs_load(OptRunsLds& s, const int* __restrict__ tab, int nruns) {
+  nruns = nruns < 1 ? 1 : (nruns > kOptMaxRuns ? kOptMaxRuns : nruns);
+  for (int r = threadIdx.x; r < nruns; r += blockDim.x) {
+    s.start[r] = tab[r];
+    s.wd[r] = __int_as_float(tab[nruns + 1 + r]);
+    s.lm[r] = __int_as_float(tab[2 * nruns + 1 + r]);
+  }
+  __syncthreads();
+  return nruns;
+}
+// the run of flat index idx: the largest r in [0, nruns) with start[r] <= idx (0 when there is none)
+__device__ __forceinline__ int opt_run_of(const OptRunsLds& s, int nruns, int idx) {
+  int lo = 0;
+  for (int len = nruns; len > 1;) {  // (len is wave-uniform; lo + half < lo + len <= nruns)
+    const int half = len >> 1;
+    if (s.start[lo + half] <= idx) lo += half;
+    len -= half;
+  }
+  return lo < 0 ? 0 : (lo >= nruns ? nruns - 1 : lo);
+}
+
+template <bool EMA, bool GROUPS>
 __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v,
                            bf16* __restrict__ p16, long long n, const float* __restrict__ hyper, float lr, float mom,
                            float damp, float wd, int nesterov, int first, const float* __restrict__ gscale_ptr,
-                           float gscale, EmaArgs<EMA> ea) {
+                           float gscale, EmaArgs<EMA> ea, GroupArgs<GROUPS> ga) {
   // hyper (device, nullable): [lr] so a captured graph follows the LR schedule on replay
   if (hyper) lr = hyper[0];
+  [[maybe_unused]] int nruns = 0;
+  [[maybe_unused]] OptRunsLds* runs = nullptr;
+  if constexpr (GROUPS) {
+    __shared__ OptRunsLds s_runs;
+    runs = &s_runs;
+    nruns = opt_runs_load(s_runs, ga.tab, ga.nruns);
+  }
   [[maybe_unused]] float* __restrict__ ema = nullptr;
   [[maybe_unused]] float omd = 0.f;
   if constexpr (EMA) {
@@ -829,16 +872,22 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i * 4 < n; i += (long long)gridDim.x * blockDim.x) {
     const long long e = i * 4;
     if (e + 4 <= n) {
+      float wd_r = wd, lr_r = lr;  // this vector's run (GROUPS); the launch's scalars otherwise
+      if constexpr (GROUPS) {
+        const int r = opt_run_of(*runs, nruns, ga.run_base + (int)e);
+        wd_r = runs->wd[r];
+        lr_r = lr * runs->lm[r];
+      }
       f32x4 pp = *reinterpret_cast<f32x4*>(p + e);
       f32x4 gg = *reinterpret_cast<const f32x4*>(g + e) * gs;
-      gg += wd * pp;
+      gg += wd_r * pp;
       f32x4 d = gg;
       if (mom != 0.f) {
         f32x4 vv = first ? gg : (*reinterpret_cast<f32x4*>(v + e) * mom + (1.f - damp) * gg);
         *reinterpret_cast<f32x4*>(v + e) = vv;
         d = nesterov ? gg + mom * vv : vv;
       }
-      pp -= lr * d;
+      pp -= lr_r * d;
       *reinterpret_cast<f32x4*>(p + e) = pp;
       if (p16) {
         bf16x4 b = {(bf16)pp[0], (bf16)pp[1], (bf16)pp[2], (bf16)pp[3]};
@@ -852,14 +901,20 @@ __global__ void sgd_kernel(float* __restrict__ p, const float* __restrict__ g, f
       }
     } else {
       for (long long k = e; k < n; ++k) {
-        float gg = g[k] * gs + wd * p[k];
+        float wd_r = wd, lr_r = lr;  // (the tail resolves its run per element)
+        if constexpr (GROUPS) {
+          const int r = opt_run_of(*runs, nruns, ga.run_base + (int)k);
+          wd_r = runs->wd[r];
+          lr_r = lr * runs->lm[r];
+        }
+        float gg = g[k] * gs + wd_r * p[k];
         float d = gg;
         if (mom != 0.f) {
           const float vv = first ? gg : v[k] * mom + (1.f - damp) * gg;
           v[k] = vv;
           d = nesterov ? gg + mom * vv : vv;
         }
-        p[k] -= lr * d;
+        p[k] -= lr_r * d;
         if (p16) p16[k] = (bf16)p[k];
         if constexpr (EMA) ema[k] = ema_lerp(ema[k], p[k], omd);
       }
@@ -926,13 +981,21 @@ __global__ void lars_apply_kernel(const float* __restrict__ p, float* __restrict
     g[off + i] = scale * g[off + i] + decay * p[off + i];
 }
 
-template <bool EMA>
+template <bool EMA, bool GROUPS>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, bf16* __restrict__ p16, long long n, const float* __restrict__ hyper,
                             float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2,
-                            const float* __restrict__ gscale_ptr, float gscale, EmaArgs<EMA> ea) {
+                            const float* __restrict__ gscale_ptr, float gscale, EmaArgs<EMA> ea,
+                            GroupArgs<GROUPS> ga) {
   // hyper (device, nullable): [lr, 1-b1^t, 1-b2^t] so graph replays track the step count
   if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2 = hyper[2]; }
+  [[maybe_unused]] int nruns = 0;
+  [[maybe_unused]] OptRunsLds* runs = nullptr;
+  if constexpr (GROUPS) {
+    __shared__ OptRunsLds s_runs;
+    runs = &s_runs;
+    nruns = opt_runs_load(s_runs, ga.tab, ga.nruns);
+  }
   [[maybe_unused]] float* __restrict__ ema = nullptr;
   [[maybe_unused]] float omd = 0.f;
   if constexpr (EMA) {
@@ -941,14 +1004,20 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   }
   const float gs = gscale_ptr ? gscale * gscale_ptr[0] : gscale;
   for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (long long)gridDim.x * blockDim.x) {
+    float wd_r = wd, lr_r = lr;  // this element's run (GROUPS); the launch's scalars otherwise
+    if constexpr (GROUPS) {
+      const int r = opt_run_of(*runs, nruns, ga.run_base + (int)k);
+      wd_r = runs->wd[r];
+      lr_r = lr * runs->lm[r];
+    }
     float gg = g[k] * gs;
     float pp = p[k];
-    if (decoupled) pp -= lr * wd * pp;
-    else gg += wd * pp;
+    if (decoupled) pp -= lr_r * wd_r * pp;
+    else gg += wd_r * pp;
     const float mm = b1 * m[k] + (1.f - b1) * gg;
     const float vv = b2 * v[k] + (1.f - b2) * gg * gg;
     m[k] = mm; v[k] = vv;
-    pp -= lr * (mm / bc1) / (sqrtf(vv / bc2) + eps);
+    pp -= lr_r * (mm / bc1) / (sqrtf(vv / bc2) + eps);
     p[k] = pp;
     if (p16) p16[k] = (bf16)pp;
     if constexpr (EMA) ema[k] = ema_lerp(ema[k], pp, omd);
@@ -1522,36 +1591,90 @@ extern "C" int dbx_ce_eval(const void* logits, int is_bf16, const long long* lab
                        nvalid, loss_out, rank_out);
   RET_LAST;
 }
+// SGD / Adam launches: <EMA, GROUPS> in all four combinations (the plain ones are what they were). The grouped
+// kernels keep the plain grid (up to 8192 blocks): capped at the 2048 blocks resident at once, so that each
+// stages its table once for four times the trips, they ran 15-30 % slower (profiles/param_groups/).
+template <bool EMA, bool GROUPS>
+static int sgd_launch(float* p, const float* g, float* v, bf16* p16, long long n, const float* hyper, float lr,
+                      float mom, float damp, float wd, int nesterov, int first, const float* gscale_ptr, float gscale,
+                      EmaArgs<EMA> ea, GroupArgs<GROUPS> ga, hipStream_t st) {
+  hipLaunchKernelGGL((sgd_kernel<EMA, GROUPS>), dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, v, p16, n, hyper,
+                     lr, mom, damp, wd, nesterov, first, gscale_ptr, gscale, ea, ga);
+  RET_LAST;
+}
+template <bool EMA, bool GROUPS>
+static int adam_launch(float* p, const float* g, float* m, float* v, bf16* p16, long long n, const float* hyper,
+                       float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2,
+                       const float* gscale_ptr, float gscale, EmaArgs<EMA> ea, GroupArgs<GROUPS> ga, hipStream_t st) {
+  hipLaunchKernelGGL((adam_kernel<EMA, GROUPS>), dim3(grid_for(n)), dim3(256), 0, st, p, g, m, v, p16, n, hyper, lr, b1,
+                     b2, eps, wd, decoupled, bc1, bc2, gscale_ptr, gscale, ea, ga);
+  RET_LAST;
+}
+// the run table's launch-side checks (its contents are validated by the Python wrapper, once per table)
+static bool opt_runs_ok(const int* tab, int nruns, long long run_base, long long n) {
+  return tab && nruns >= 1 && nruns <= kOptMaxRuns && run_base >= 0 && run_base % 4 == 0 &&
+         run_base + n <= 0x7fffffffLL;
+}
 extern "C" int dbx_sgd(float* p, const float* g, float* v, bf16* p16, long long n, const float* hyper, float lr,
                        float mom, float damp, float wd, int nesterov, int first, const float* gscale_ptr, float gscale,
                        hipStream_t st) {
-  hipLaunchKernelGGL(sgd_kernel<false>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, v, p16, n, hyper, lr, mom,
-                     damp, wd, nesterov, first, gscale_ptr, gscale, EmaArgs<false>{});
-  RET_LAST;
+  return sgd_launch<false, false>(p, g, v, p16, n, hyper, lr, mom, damp, wd, nesterov, first, gscale_ptr, gscale,
+                                  EmaArgs<false>{}, GroupArgs<false>{}, st);
 }
 extern "C" int dbx_adam(float* p, const float* g, float* m, float* v, bf16* p16, long long n, const float* hyper,
                         float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2,
                         const float* gscale_ptr, float gscale, hipStream_t st) {
-  hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_for(n)), dim3(256), 0, st, p, g, m, v, p16, n, hyper, lr, b1, b2, eps,
-                     wd, decoupled, bc1, bc2, gscale_ptr, gscale, EmaArgs<false>{});
-  RET_LAST;
+  return adam_launch<false, false>(p, g, m, v, p16, n, hyper, lr, b1, b2, eps, wd, decoupled, bc1, bc2, gscale_ptr,
+                                   gscale, EmaArgs<false>{}, GroupArgs<false>{}, st);
 }
 extern "C" int dbx_sgd_ema(float* p, const float* g, float* v, bf16* p16, long long n, const float* hyper, float lr,
                            float mom, float damp, float wd, int nesterov, int first, const float* gscale_ptr,
                            float gscale, float* ema, const float* omd_ptr, float omd, hipStream_t st) {
   if (!ema) return -1;
-  hipLaunchKernelGGL(sgd_kernel<true>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, st, p, g, v, p16, n, hyper, lr, mom,
-                     damp, wd, nesterov, first, gscale_ptr, gscale, EmaArgs<true>{ema, omd_ptr, omd});
-  RET_LAST;
+  return sgd_launch<true, false>(p, g, v, p16, n, hyper, lr, mom, damp, wd, nesterov, first, gscale_ptr, gscale,
+                                 EmaArgs<true>{ema, omd_ptr, omd}, GroupArgs<false>{}, st);
 }
 extern "C" int dbx_adam_ema(float* p, const float* g, float* m, float* v, bf16* p16, long long n, const float* hyper,
                             float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2,
                             const float* gscale_ptr, float gscale, float* ema, const float* omd_ptr, float omd,
                             hipStream_t st) {
   if (!ema) return -1;
-  hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n)), dim3(256), 0, st, p, g, m, v, p16, n, hyper, lr, b1, b2, eps,
-                     wd, decoupled, bc1, bc2, gscale_ptr, gscale, EmaArgs<true>{ema, omd_ptr, omd});
-  RET_LAST;
+  return adam_launch<true, false>(p, g, m, v, p16, n, hyper, lr, b1, b2, eps, wd, decoupled, bc1, bc2, gscale_ptr,
+                                  gscale, EmaArgs<true>{ema, omd_ptr, omd}, GroupArgs<false>{}, st);
+}
+// grouped forms: wd and lr_mult per run of the flat buffer (tab / nruns / run_base: see GroupArgs)
+extern "C" int dbx_sgd_groups(float* p, const float* g, float* v, bf16* p16, long long n, const float* hyper, float lr,
+                              float mom, float damp, int nesterov, int first, const float* gscale_ptr, float gscale,
+                              const int* tab, int nruns, long long run_base, hipStream_t st) {
+  if (!opt_runs_ok(tab, nruns, run_base, n)) return -1;
+  return sgd_launch<false, true>(p, g, v, p16, n, hyper, lr, mom, damp, 0.f, nesterov, first, gscale_ptr, gscale,
+                                 EmaArgs<false>{}, GroupArgs<true>{tab, nruns, (int)run_base}, st);
+}
+extern "C" int dbx_sgd_groups_ema(float* p, const float* g, float* v, bf16* p16, long long n, const float* hyper,
+                                  float lr, float mom, float damp, int nesterov, int first, const float* gscale_ptr,
+                                  float gscale, const int* tab, int nruns, long long run_base, float* ema,
+                                  const float* omd_ptr, float omd, hipStream_t st) {
+  if (!ema || !opt_runs_ok(tab, nruns, run_base, n)) return -1;
+  return sgd_launch<true, true>(p, g, v, p16, n, hyper, lr, mom, damp, 0.f, nesterov, first, gscale_ptr, gscale,
+                                EmaArgs<true>{ema, omd_ptr, omd}, GroupArgs<true>{tab, nruns, (int)run_base}, st);
+}
+extern "C" int dbx_adam_groups(float* p, const float* g, float* m, float* v, bf16* p16, long long n,
+                               const float* hyper, float lr, float b1, float b2, float eps, int decoupled, float bc1,
+                               float bc2, const float* gscale_ptr, float gscale, const int* tab, int nruns,
+                               long long run_base, hipStream_t st) {
+  if (!opt_runs_ok(tab, nruns, run_base, n)) return -1;
+  return adam_launch<false, true>(p, g, m, v, p16, n, hyper, lr, b1, b2, eps, 0.f, decoupled, bc1, bc2, gscale_ptr,
+                                  gscale, EmaArgs<false>{}, GroupArgs<true>{tab, nruns, (int)run_base}, st);
+}
+extern "C" int dbx_adam_groups_ema(float* p, const float* g, float* m, float* v, bf16* p16, long long n,
+                                   const float* hyper, float lr, float b1, float b2, float eps, int decoupled,
+                                   float bc1, float bc2, const float* gscale_ptr, float gscale, const int* tab,
+                                   int nruns, long long run_base, float* ema, const float* omd_ptr, float omd,
+                                   hipStream_t st) {
+  if (!ema || !opt_runs_ok(tab, nruns, run_base, n)) return -1;
+  return adam_launch<true, true>(p, g, m, v, p16, n, hyper, lr, b1, b2, eps, 0.f, decoupled, bc1, bc2, gscale_ptr,
+                                 gscale, EmaArgs<true>{ema, omd_ptr, omd}, GroupArgs<true>{tab, nruns, (int)run_base},
+                                 st);
 }
 extern "C" int dbx_ema_update(float* e, const float* p, long long n, const float* omd_ptr, float omd,
                               hipStream_t st) {

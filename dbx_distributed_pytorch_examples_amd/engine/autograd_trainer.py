@@ -16,7 +16,16 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..config import distinct_param_groups, has_param_groups, resolve_param_groups
 from ..parallel.ddp import DistributedDataParallel, flat_view, unwrap
+
+
+def _single_group(params, who: str):
+    """LARS and LAMB decide decay and adaptation per tensor themselves: no torch param groups."""
+    params = list(params)
+    if params and isinstance(params[0], dict):
+        raise ValueError(f"{who} has its own per-tensor decay / adapt rule and takes no parameter groups")
+    return params
 
 
 class LARS(torch.optim.Optimizer):
@@ -25,6 +34,7 @@ class LARS(torch.optim.Optimizer):
     plain gradient without decay. Same math as the native ``lars_scale`` + ``sgd_step`` kernels."""
 
     def __init__(self, params, lr, momentum=0.9, weight_decay=0.0, trust_coefficient=0.001, nesterov=False):
+        params = _single_group(params, "LARS")
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, eta=trust_coefficient,
                                       nesterov=nesterov))
 
@@ -59,6 +69,7 @@ class LAMB(torch.optim.Optimizer):
 
     def __init__(self, params, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, adapt_1d=False, trust_min=0.0,
                  trust_max=0.0):
+        params = _single_group(params, "LAMB")
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay,
                                       adapt_1d=bool(adapt_1d), trust_min=trust_min, trust_max=trust_max))
 
@@ -90,7 +101,33 @@ class LAMB(torch.optim.Optimizer):
                 p.add_(u, alpha=-grp["lr"])
 
 
-def build_torch_optimizer(params, o):
+def param_kinds(model: nn.Module) -> dict:
+    """``{parameter name: kind}`` for config.resolve_param_groups: "norm" for the direct parameters of a
+    normalisation layer, "bias" for any other parameter named ``bias``, else "weight"."""
+    norm = (nn.modules.batchnorm._NormBase, nn.GroupNorm, nn.LayerNorm)
+    norm_ids = {id(p) for m in model.modules() if isinstance(m, norm) for p in m.parameters(recurse=False)}
+    return {n: "norm" if id(p) in norm_ids else "bias" if n.split(".")[-1] == "bias" else "weight"
+            for n, p in model.named_parameters()}
+
+
+def build_torch_optimizer(params, o, model: Optional[nn.Module] = None):
+    """``params``: parameters, or ``(name, parameter)`` pairs as ``model.named_parameters()`` gives them.
+    With parameter groups in ``o`` (config.resolve_param_groups; needs the pairs and ``model`` for the
+    kinds) one torch param group per distinct (weight_decay, lr_mult): ``lr = o.lr * lr_mult`` and an
+    ``lr_mult`` entry that ``AutogradTrainer.set_lr`` keeps applying."""
+    params = list(params)
+    named = bool(params) and isinstance(params[0], tuple)
+    if has_param_groups(o):
+        if o.name in ("lars", "lamb"):
+            raise ValueError(f"{o.name.upper()} has its own per-tensor decay / adapt rule and takes no parameter groups")
+        if not named or model is None:
+            raise ValueError("parameter groups need named parameters and the model (for the parameter kinds)")
+        kinds = param_kinds(model)
+        values = resolve_param_groups([(n, kinds.get(n, "weight")) for n, _ in params], o)
+        params = [{"params": [p for (_, p), v in zip(params, values) if v == (wd, lm)], "weight_decay": wd,
+                   "lr": o.lr * lm, "lr_mult": lm} for wd, lm in distinct_param_groups(values)]
+    elif named:
+        params = [p for _, p in params]
     if o.name == "lamb":
         return LAMB(params, lr=o.lr, betas=tuple(o.betas), eps=o.eps, weight_decay=o.weight_decay,
                     adapt_1d=getattr(o, "adapt_1d", False), trust_min=getattr(o, "trust_min", 0.0),
@@ -161,7 +198,8 @@ class AutogradTrainer:
         self.grad_accum = max(1, grad_accum)
         self.num_classes = getattr(unwrap(model), "num_classes", None)
         self.zero = None
-        params = [p for p in self.model.parameters() if p.requires_grad]
+        named = [(n, p) for n, p in self.model.named_parameters() if p.requires_grad]
+        params = [p for _, p in named]
         if self.sharded:
             self.opt = None
         elif zero_stage and params:
@@ -174,7 +212,7 @@ class AutogradTrainer:
                                              grad_scale=1.0)  # DDP already averaged
             self.opt = None
         else:
-            self.opt = build_torch_optimizer(params, optim) if params else None
+            self.opt = build_torch_optimizer(named, optim, self.model) if params else None
         self.micro = 0
         self.loss_sum = torch.zeros((), device=device)
         self.correct = torch.zeros((), device=device)
@@ -184,7 +222,7 @@ class AutogradTrainer:
         self.o.lr = lr
         if self.opt is not None:
             for g in self.opt.param_groups:
-                g["lr"] = lr
+                g["lr"] = lr * g.get("lr_mult", 1.0)
 
     def _loss(self, out, x, y, target=None):
         m = unwrap(self.model)

@@ -38,6 +38,7 @@ from ..config import OptimizerConfig
 from ..models.wrappers import FrozenBackboneClassifier
 from ..parallel.ddp import DistributedDataParallel
 from ..utils import debug as _debug
+from ..config import reject_param_groups
 from .autograd_trainer import build_torch_optimizer
 from .hyper import DeviceHyper
 from .program import ResNetProgram, release_dead_graphs
@@ -158,6 +159,7 @@ class FrozenFeatureTrainer:
         self.dev = device
         self.prog = ResNetProgram(_backbone_proxy(model), batch, image_hw, device, src_hw=src_hw, mean=mean, std=std)
         self.prog.training = False
+        reject_param_groups(optim, "the frozen-backbone trainer (only the head trains)")
         self.prog.prepare_weights()  # frozen: converted once
         self.head = model.resnet.fc.to(device)
         self.smoothing = label_smoothing

@@ -23,13 +23,14 @@ from __future__ import annotations
 
 import math
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
+from ..config import distinct_param_groups, has_param_groups, resolve_param_groups
 from ..engine_config import EngineConfig
 from ..ops import kernels as K
 from ..parallel.dist import host_sync_for_gloo
@@ -54,6 +55,10 @@ class OptimConfig:
     adapt_1d: bool = False       # LAMB: also decay and adapt BN affine parameters and biases (FusedLamb / apex)
     trust_min: float = 0.0       # LAMB trust-ratio clamp where adapted (0 = unbounded)
     trust_max: float = 0.0
+    # parameter groups (sgd | adam | adamw at zero_stage 0; config.resolve_param_groups)
+    groups: list = field(default_factory=list)  # [{match, weight_decay?, lr_mult?}, ...]: first match wins
+    norm_weight_decay: float = -1.0  # < 0: weight_decay. Every parameter of a normalisation layer
+    bias_weight_decay: float = -1.0  # < 0: weight_decay. Biases of all other layers (fc.bias)
 
 
 @dataclass
@@ -84,6 +89,13 @@ class NativeTrainer:
             raise ValueError("LARS runs on the full flat buffer; use zero_stage=0")
         if zero_stage and optim.name == "lamb":
             raise ValueError("LAMB needs every tensor's norms on the full flat buffer; use zero_stage=0")
+        if has_param_groups(optim):
+            if optim.name in ("lars", "lamb"):
+                raise ValueError(f"{optim.name.upper()} has its own per-tensor decay / adapt rule; parameter groups "
+                                 f"(groups / norm_weight_decay / bias_weight_decay) work with sgd, adam and adamw")
+            if zero_stage:
+                raise ValueError("parameter groups need the contiguous flat master; use zero_stage=0 (the sharded "
+                                 "layout is not contiguous in flat coordinates)")
         self.ema_decay = float(ema_decay)
         self.ema_warmup = bool(ema_warmup)
         if not 0.0 <= self.ema_decay < 1.0:
@@ -236,6 +248,7 @@ class NativeTrainer:
             self.zero.grad_div = self.k
             self.mom = self.zero.m  # shard-sized optimizer state only
             self.mom2 = self.zero.v
+        self.group_runs, self._group_values = self._param_group_runs()
         self.lars = self._lars_segments() if optim.name == "lars" else None
         self.lamb = self._lars_segments(adapt_all=optim.adapt_1d) if optim.name == "lamb" else None
         # weight EMA (ema_decay > 0): ``ema`` shadows the flat master and is moved by the optimizer
@@ -315,6 +328,49 @@ class NativeTrainer:
             return {}
         return {"ema": self.ema[lo:hi], "ema_hyper": self.ema_hyper,
                 "ema_one_minus_decay": 1.0 - self.ema_decay}
+
+    def _param_group_runs(self):
+        """Parameter groups (OptimConfig.groups / norm_weight_decay / bias_weight_decay): every tensor's
+        (weight_decay, lr_mult), resolved from its name and kind (a BN's parameters are "norm", any other
+        ``.bias`` is "bias": the rule of _lars_segments), and the run table of the flat master the SGD / Adam
+        kernels read -- neighbours with equal values merged; the alignment padding between tensors joins
+        the run before it (master and gradient are zero there). (None, None) when nothing is set: the
+        trainer then runs exactly the plain launches."""
+        rs = self.prog.param_ranges
+        bn_names = {f"{bn.name}." for bn in self.prog.bns}
+        kinds = [(r[0], "norm" if any(r[0].startswith(b) for b in bn_names)
+                  else "bias" if r[0].endswith(".bias") else "weight") for r in rs]
+        values = resolve_param_groups(kinds, self.opt)
+        if values is None:
+            return None, None
+        runs = []
+        for (_, off, _), val in sorted(zip(rs, values), key=lambda t: t[0][1]):
+            if not runs:
+                runs.append((0,) + val)
+            elif val != runs[-1][1:]:
+                runs.append((off,) + val)
+        return K.pack_opt_runs(runs, self.prog.n_params, self.dev), values
+
+    def param_group_table(self):
+        """``[(name, weight_decay, lr_mult)]`` per parameter tensor, in flat-buffer order: what the optimizer
+        applies (without groups: the one weight decay and 1.0; LARS / LAMB keep their own rule)."""
+        rs = self.prog.param_ranges
+        values = self._group_values or [(float(self.opt.weight_decay), 1.0)] * len(rs)
+        return [(r[0], wd, lm) for r, (wd, lm) in zip(rs, values)]
+
+    def param_group_summary(self):
+        """``[(weight_decay, lr_mult, tensors, elements)]`` per distinct group, for the log."""
+        rs, tab = self.prog.param_ranges, self.param_group_table()
+        return [(wd, lm, sum(1 for t in tab if t[1:] == (wd, lm)),
+                 sum(r[2] for r, t in zip(rs, tab) if t[1:] == (wd, lm)))
+                for wd, lm in distinct_param_groups([t[1:] for t in tab])]
+
+    def _wd_kw(self, lo: int) -> dict:
+        """The weight-decay arguments of an SGD / Adam launch over master[lo:]: the scalar, or with
+        parameter groups the run table (which carries the decays) and the slice's place in it."""
+        if self.group_runs is None:
+            return {"weight_decay": self.opt.weight_decay}
+        return {"weight_decay": 0.0, "runs": self.group_runs, "run_base": lo}
 
     def _segment_ranges(self):
         """Contiguous [lo, hi) of every backward segment's gradients (None: no parameters)."""
@@ -415,11 +471,11 @@ class NativeTrainer:
         gscale = 1.0 / (self.world * self.loopback * self.k)
         if o.name == "sgd":
             K.sgd_step(p.master[lo:hi], p.grad[lo:hi], self.mom[lo:hi], None, lr=o.lr, momentum=o.momentum,
-                       dampening=o.dampening, weight_decay=o.weight_decay, nesterov=o.nesterov, first=False,
-                       grad_scale=gscale, hyper=self.hyper, **self._ema_kw(lo, hi))
+                       dampening=o.dampening, nesterov=o.nesterov, first=False,
+                       grad_scale=gscale, hyper=self.hyper, **self._wd_kw(lo), **self._ema_kw(lo, hi))
         else:
             K.adam_step(p.master[lo:hi], p.grad[lo:hi], self.mom[lo:hi], self.mom2[lo:hi], None, lr=o.lr,
-                        beta1=o.betas[0], beta2=o.betas[1], eps=o.eps, weight_decay=o.weight_decay,
+                        beta1=o.betas[0], beta2=o.betas[1], eps=o.eps, **self._wd_kw(lo),
                         decoupled=(o.name == "adamw"), step=1, grad_scale=gscale, hyper=self.hyper,
                         **self._ema_kw(lo, hi))
 
@@ -547,11 +603,11 @@ class NativeTrainer:
             return
         if o.name == "sgd":
             K.sgd_step(p.master, p.grad, self.mom, None, lr=o.lr, momentum=o.momentum, dampening=o.dampening,
-                       weight_decay=o.weight_decay, nesterov=o.nesterov, first=False, grad_scale_ptr=gsp,
-                       grad_scale=gscale, hyper=self.hyper, **self._ema_kw(0, p.n_params))
+                       nesterov=o.nesterov, first=False, grad_scale_ptr=gsp,
+                       grad_scale=gscale, hyper=self.hyper, **self._wd_kw(0), **self._ema_kw(0, p.n_params))
         else:
             K.adam_step(p.master, p.grad, self.mom, self.mom2, None, lr=o.lr, beta1=o.betas[0], beta2=o.betas[1],
-                        eps=o.eps, weight_decay=o.weight_decay, decoupled=(o.name == "adamw"), step=1,
+                        eps=o.eps, **self._wd_kw(0), decoupled=(o.name == "adamw"), step=1,
                         grad_scale_ptr=gsp, grad_scale=gscale, hyper=self.hyper, **self._ema_kw(0, p.n_params))
 
     # ----------------------------------------------------------------------------------

@@ -351,8 +351,10 @@ class ResNetProgram:
                     raise TypeError(f"unsupported block {type(blk).__name__}")
                 dsc = dsb = None
                 if ds is not None:
-                    dsc = self._conv(f"{pre}.downsample.0", ds[0], h, w)
-                    dsb = BNL(f"{pre}.downsample.1", ds[1], ds[1].num_features)
+                    # (named as model.named_parameters() names them: optimizer groups match on these)
+                    dsn = "skip_connection" if isinstance(blk, CifarBlock) else "downsample"
+                    dsc = self._conv(f"{pre}.{dsn}.0", ds[0], h, w)
+                    dsb = BNL(f"{pre}.{dsn}.1", ds[1], ds[1].num_features)
                 last = convs[-1]
                 blk_l = BlockL(kind, convs, bns, dsc, dsb, (h, w, c), (last.OH, last.OW, last.OC))
                 self.blocks.append(blk_l)

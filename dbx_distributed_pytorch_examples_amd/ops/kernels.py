@@ -1357,18 +1357,51 @@ def dropout(x, y, p, seed, offset):
     return y
 
 
+OPT_MAX_RUNS = _ref.OPT_MAX_RUNS  # csrc/nn_ops.hip kOptMaxRuns
+pack_opt_runs = _ref.pack_opt_runs
+
+
+def _chk_opt_runs(runs, n: int, run_base: int, weight_decay: float, what: str, f32, p16) -> Tuple[int, int, int]:
+    """A grouped launch's host checks: the table (validated once per tensor object, see
+    ``reference.check_opt_runs``; never read back by a captured or replayed step), the slice inside it, and
+    the alignment :func:`lamb_step` asks for (16 bytes per lane from every base)."""
+    starts, _, _ = _ref.check_opt_runs(runs, n, run_base, weight_decay, what)
+    if runs.device != f32[0][0].device:
+        raise ValueError(f"{what}: runs is on {runs.device}, p on {f32[0][0].device}")
+    for t, nm in f32:
+        if t.data_ptr() % 16:
+            raise ValueError(f"{nm}: {what} with runs needs a 16-byte aligned slice")
+    if p16 is not None and p16.data_ptr() % 8:
+        raise ValueError(f"p16: {what} with runs needs an 8-byte aligned slice")
+    return runs.data_ptr(), len(starts) - 1, int(run_base)
+
+
 @_dispatch
 def sgd_step(p, g, v, p16=None, *, lr, momentum, dampening=0.0, weight_decay=0.0, nesterov=False, first=False,
-             grad_scale_ptr=None, grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0):
+             grad_scale_ptr=None, grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0,
+             runs=None, run_base=0):
     """PyTorch-SGD semantics. ``hyper`` (fp32[1] device tensor) overrides ``lr`` at run time. ``ema``
     (flat fp32, the size of ``p``): the same launch also moves the weight average towards the updated
-    parameter, ``e = fma(omd, p_new - e, e)`` (see :func:`ema_update` for ``omd``)."""
+    parameter, ``e = fma(omd, p_new - e, e)`` (see :func:`ema_update` for ``omd``). ``runs`` (the table of
+    :func:`pack_opt_runs`): parameter groups -- element i takes the weight decay ``wd[r]`` and the learning
+    rate ``lr * lr_mult[r]`` of the run r that holds flat index ``run_base + i`` (``run_base``: where ``p[0]``
+    sits in the buffer the table describes, a multiple of 4); ``weight_decay`` must then stay 0."""
     n = p.numel()
     _chk(p, torch.float32, "p")
     _chk(g, torch.float32, "g", n)
     _chk(v, torch.float32, "v", n)
     if p16 is not None:
         _chk(p16, torch.bfloat16, "p16", n)
+    if runs is not None:
+        tab = _chk_opt_runs(runs, n, run_base, weight_decay, "sgd_step", ((p, "p"), (g, "g"), (v, "v")), p16)
+        args = (p.data_ptr(), g.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr), float(momentum),
+                float(dampening), int(nesterov), int(first), _p(grad_scale_ptr), float(grad_scale), *tab)
+        if ema is not None:
+            _chk_ema(ema, n, ema_hyper)
+            C().sgd_groups_ema(*args, ema.data_ptr(), _p(ema_hyper), float(ema_one_minus_decay), stream_ptr())
+            return
+        C().sgd_groups(*args, stream_ptr())
+        return
     if ema is not None:
         _chk_ema(ema, n, ema_hyper)
         C().sgd_ema(p.data_ptr(), g.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr), float(momentum),
@@ -1410,14 +1443,31 @@ def lars_scale(p, g, seg_off, seg_len, adapt, norms, *, grad_scale, eta, weight_
 
 @_dispatch
 def adam_step(p, g, m, v, p16=None, *, lr, beta1, beta2, eps, weight_decay, decoupled, step,
-              grad_scale_ptr=None, grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0):
+              grad_scale_ptr=None, grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0,
+              runs=None, run_base=0):
     """Adam / AdamW. ``hyper`` (fp32[3] device: lr, 1-b1^t, 1-b2^t) overrides lr/step at run time.
-    ``ema`` / ``ema_hyper`` / ``ema_one_minus_decay``: the fused weight average, as in :func:`sgd_step`."""
+    ``ema`` / ``ema_hyper`` / ``ema_one_minus_decay``: the fused weight average, as in :func:`sgd_step`.
+    ``runs`` / ``run_base``: parameter groups, as in :func:`sgd_step` (the decoupled decay is
+    ``p -= (lr * lr_mult[r]) * wd[r] * p``, torch's AdamW with the group's lr)."""
     n = p.numel()
     for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
         _chk(t, torch.float32, nm, n)
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
+    if runs is not None:
+        if p16 is not None:
+            _chk(p16, torch.bfloat16, "p16", n)
+        tab = _chk_opt_runs(runs, n, run_base, weight_decay, "adam_step",
+                            ((p, "p"), (g, "g"), (m, "m"), (v, "v")), p16)
+        args = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr),
+                float(beta1), float(beta2), float(eps), int(decoupled), float(bc1), float(bc2), _p(grad_scale_ptr),
+                float(grad_scale), *tab)
+        if ema is not None:
+            _chk_ema(ema, n, ema_hyper)
+            C().adam_groups_ema(*args, ema.data_ptr(), _p(ema_hyper), float(ema_one_minus_decay), stream_ptr())
+            return
+        C().adam_groups(*args, stream_ptr())
+        return
     if ema is not None:
         _chk_ema(ema, n, ema_hyper)
         C().adam_ema(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr),

@@ -473,12 +473,92 @@ def ce_eval(logits, labels, stats, k, nvalid=None, loss_out=None, rank_out=None)
         rank_out.copy_(torch.where(valid, rank, torch.full_like(rank, -1)).view_as(rank_out))
 
 
+OPT_MAX_RUNS = 1024  # csrc/nn_ops.hip kOptMaxRuns (the run table lives in LDS)
+
+
+def _validate_opt_runs(starts, wds, lms, what: str = "pack_opt_runs") -> None:
+    """``starts`` = start[0..nruns] (the last entry is n_total)."""
+    nruns = len(starts) - 1
+    if nruns < 1:
+        raise ValueError(f"{what}: the run table is empty")
+    if nruns > OPT_MAX_RUNS:
+        raise ValueError(f"{what}: {nruns} runs, the kernels take at most {OPT_MAX_RUNS}")
+    if starts[0] != 0:
+        raise ValueError(f"{what}: the first run must start at 0, got {starts[0]}")
+    if any(s % 4 for s in starts[:-1]):
+        raise ValueError(f"{what}: every run start must be a multiple of 4 elements")
+    if any(b <= a for a, b in zip(starts, starts[1:])):
+        raise ValueError(f"{what}: run starts must be strictly increasing and below n_total={starts[-1]}")
+    if starts[-1] >= 2 ** 31:
+        raise ValueError(f"{what}: n_total={starts[-1]} does not fit the table's int32 indices")
+    for nm, vals in (("weight_decay", wds), ("lr_mult", lms)):
+        if any(not math.isfinite(x) or x < 0 for x in vals):
+            raise ValueError(f"{what}: {nm} values must be finite and >= 0")
+
+
+def pack_opt_runs(runs, n_total: int, device=None) -> torch.Tensor:
+    """The run table of :func:`sgd_step` / :func:`adam_step` (``runs=``) from ``[(start, weight_decay, lr_mult)]``:
+    run r covers flat indices [start[r], start[r+1]) and the last one ends at ``n_total``. Starts are strictly
+    increasing multiples of 4 from 0; at most ``OPT_MAX_RUNS`` runs (merge equal neighbours first). One int32
+    tensor ``start[nruns + 1] | wd[nruns] | lr_mult[nruns]`` (the last two as fp32 bits). Validated here, on
+    the host: a step that uses the table never reads it back."""
+    runs = [(int(s), float(w), float(m)) for s, w, m in runs]
+    starts = [r[0] for r in runs] + [int(n_total)]
+    wds, lms = [r[1] for r in runs], [r[2] for r in runs]
+    _validate_opt_runs(starts, wds, lms)
+    f = torch.tensor(wds + lms, dtype=torch.float32).view(torch.int32)
+    tab = torch.cat([torch.tensor(starts, dtype=torch.int32), f]).to(device)
+    tab._dbx_runs = (tab._version, starts, wds, lms)
+    return tab
+
+
+def check_opt_runs(tab, n: int, run_base: int, weight_decay: float, what: str):
+    """Host checks of a grouped optimizer call; returns (starts, wds, lms) as host lists. The table is
+    validated (and read back, unless :func:`pack_opt_runs` built it) once per tensor object and version."""
+    if not isinstance(tab, torch.Tensor) or tab.dtype != torch.int32 or tab.dim() != 1 or not tab.is_contiguous() \
+            or tab.numel() < 4 or (tab.numel() - 1) % 3:
+        raise TypeError(f"{what}: runs must be the int32 table of pack_opt_runs")
+    if float(weight_decay) != 0.0:
+        raise ValueError(f"{what}: with runs the table carries the (absolute) weight decays; leave weight_decay at 0.0")
+    ok = getattr(tab, "_dbx_runs", None)
+    if ok is None or ok[0] != tab._version:
+        nruns = (tab.numel() - 1) // 3
+        host = tab.cpu()
+        starts = host[:nruns + 1].tolist()
+        f = host[nruns + 1:].view(torch.float32).tolist()
+        _validate_opt_runs(starts, f[:nruns], f[nruns:], what)
+        ok = tab._dbx_runs = (tab._version, starts, f[:nruns], f[nruns:])
+    _, starts, wds, lms = ok
+    run_base = int(run_base)
+    if run_base % 4:
+        raise ValueError(f"{what}: run_base={run_base} must be a multiple of 4 elements")
+    if run_base < 0 or run_base + n > starts[-1]:
+        raise ValueError(f"{what}: the table covers [0, {starts[-1]}), the slice is [{run_base}, {run_base + n})")
+    return starts, wds, lms
+
+
+def _expand_opt_runs(starts, vals, lo: int, hi: int, device) -> torch.Tensor:
+    """One fp32 value per element of [lo, hi) (values rounded to fp32 as the device table holds them)."""
+    out = torch.empty(hi - lo, dtype=torch.float32, device=device)
+    for r, val in enumerate(vals):
+        a, b = max(starts[r], lo), min(starts[r + 1], hi)
+        if a < b:
+            out[a - lo:b - lo] = val
+    return out
+
+
 def sgd_step(p, g, v, p16=None, *, lr, momentum, dampening=0.0, weight_decay=0.0, nesterov=False, first=False,
-             grad_scale_ptr=None, grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0):
+             grad_scale_ptr=None, grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0,
+             runs=None, run_base=0):
     if ema is not None:
         _chk_ema_pair(ema, p, "sgd_step")
     if hyper is not None:
         lr = float(hyper[0])
+    if runs is not None:  # per-element fp32 wd and lr * lr_mult vectors, otherwise the plain formula
+        n = p.numel()
+        starts, wds, lms = check_opt_runs(runs, n, run_base, weight_decay, "sgd_step")
+        weight_decay = _expand_opt_runs(starts, wds, run_base, run_base + n, p.device)
+        lr = torch.tensor(lr, dtype=torch.float32) * _expand_opt_runs(starts, lms, run_base, run_base + n, p.device)
     gs = grad_scale * (float(grad_scale_ptr[0]) if grad_scale_ptr is not None else 1.0)
     d = g * gs + weight_decay * p
     if momentum != 0:
@@ -495,20 +575,31 @@ def sgd_step(p, g, v, p16=None, *, lr, momentum, dampening=0.0, weight_decay=0.0
 
 
 def adam_step(p, g, m, v, p16=None, *, lr, beta1, beta2, eps, weight_decay, decoupled, step, grad_scale_ptr=None,
-              grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0):
+              grad_scale=1.0, hyper=None, ema=None, ema_hyper=None, ema_one_minus_decay=0.0, runs=None, run_base=0):
     if ema is not None:
         _chk_ema_pair(ema, p, "adam_step")
     bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
     if hyper is not None:
         lr, bc1, bc2 = float(hyper[0]), float(hyper[1]), float(hyper[2])
+    shrink = None
+    if runs is not None:  # per-element fp32 vectors; the decoupled factor per run, formed as the scalar one is
+        n = p.numel()
+        starts, wds, lms = check_opt_runs(runs, n, run_base, weight_decay, "adam_step")
+        if decoupled:
+            shrink = _expand_opt_runs(starts, [1 - (lr * lm) * wd for wd, lm in zip(wds, lms)], run_base,
+                                      run_base + n, p.device)
+        weight_decay = _expand_opt_runs(starts, wds, run_base, run_base + n, p.device)
+        lr = torch.tensor(lr, dtype=torch.float32) * _expand_opt_runs(starts, lms, run_base, run_base + n, p.device)
     gs = grad_scale * (float(grad_scale_ptr[0]) if grad_scale_ptr is not None else 1.0)
     gg = g * gs
     if decoupled:
-        p.mul_(1 - lr * weight_decay)
+        p.mul_(shrink if shrink is not None else 1 - lr * weight_decay)
     else:
         gg = gg + weight_decay * p
-    m.mul_(beta1).add_(gg, alpha=1 - beta1)
-    v.mul_(beta2).addcmul_(gg, gg, value=1 - beta2)
+    # (1 - beta as the kernel forms it, from the fp32 beta: 1 - 0.999 in double is 4.7e-5 off 1.f - 0.999f)
+    f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))
+    m.mul_(beta1).add_(gg, alpha=1 - f32(beta1))
+    v.mul_(beta2).addcmul_(gg, gg, value=1 - f32(beta2))
     p.sub_(lr * (m / bc1) / (torch.sqrt(v / bc2) + eps))
     if p16 is not None:
         p16.copy_(p.bfloat16())

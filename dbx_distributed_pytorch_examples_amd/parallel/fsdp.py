@@ -46,6 +46,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from ..ops import kernels as K
+from ..config import reject_param_groups
 from .dist import host_sync_for_gloo
 
 
@@ -216,6 +217,7 @@ class ShardedDataParallel(nn.Module):
         if optim.name not in ("sgd", "adam", "adamw"):
             raise ValueError(f"ZeRO-3 supports sgd / adam / adamw, not {optim.name!r}")
         K.reject_dampening(optim)
+        reject_param_groups(optim, "the sharded (ZeRO) optimizer")
         self.module = module
         self.o = optim
         self.pg = process_group

@@ -40,6 +40,7 @@ import torch
 import torch.distributed as dist
 
 from ..ops import kernels as K
+from ..config import reject_param_groups
 from .dist import host_sync_for_gloo
 
 
@@ -66,6 +67,7 @@ class ZeroShardedOptimizer:
         if optim.name not in ("sgd", "adam", "adamw"):
             raise ValueError(f"sharded optimizer supports sgd / adam / adamw, not {optim.name!r}")
         K.reject_dampening(optim)
+        reject_param_groups(optim, "the sharded (ZeRO) optimizer")
         if stage == 3:
             warnings.warn("flat-buffer ZeRO: stage 3 runs as stage 2 here; parameter sharding is parallel.fsdp.ShardedDataParallel")
             stage = 2
@@ -200,6 +202,7 @@ class SegmentedZero:
         if optim.name not in ("sgd", "adam", "adamw"):
             raise ValueError(f"sharded optimizer supports sgd / adam / adamw, not {optim.name!r}")
         K.reject_dampening(optim)
+        reject_param_groups(optim, "the sharded (ZeRO) optimizer")
         if stage == 3:
             warnings.warn("native program: ZeRO stage 3 runs as stage 2 (the captured graph needs resident "
                           "parameters; parameter sharding is parallel.fsdp.ShardedDataParallel)")

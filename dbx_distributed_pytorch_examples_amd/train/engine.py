@@ -35,7 +35,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from ..config import TrainConfig, from_deepspeed, parse_duration, to_dict
+from ..config import TrainConfig, from_deepspeed, has_param_groups, parse_duration, to_dict
 from ..models import build_model
 from ..parallel import dist as ddist
 from ..parallel.sampler import ShardSampler
@@ -140,7 +140,9 @@ class _Native:
                                                       tuple(o.betas), o.eps, o.grad_clip,
                                                       trust_coefficient=o.trust_coefficient,
                                                       adapt_1d=o.adapt_1d, trust_min=o.trust_min,
-                                                      trust_max=o.trust_max),
+                                                      trust_max=o.trust_max, groups=list(o.groups),
+                                                      norm_weight_decay=o.norm_weight_decay,
+                                                      bias_weight_decay=o.bias_weight_decay),
                                     label_smoothing=cfg.data.label_smoothing, use_graphs=cfg.graphs,
                                     bucket_cap_mb=cfg.bucket_cap_mb, allreduce_dtype=ar,
                                     src_hw=(h, w), mean=mean, std=std, zero_stage=cfg.zero.stage,
@@ -322,6 +324,18 @@ def _apply_env_overrides(cfg: TrainConfig) -> TrainConfig:
     return cfg
 
 
+def _log_param_groups(runner) -> None:
+    """The distinct (weight_decay, lr_mult) groups with their parameter counts, once."""
+    tr = runner.tr
+    if hasattr(tr, "param_group_summary"):
+        rows = tr.param_group_summary()
+    else:
+        rows = [(g["weight_decay"], g.get("lr_mult", 1.0), len(g["params"]), sum(p.numel() for p in g["params"]))
+                for g in (tr.opt.param_groups if tr.opt is not None else [])]
+    for wd, lm, nt, ne in rows:
+        _log(f"[train] param group weight_decay={wd:g} lr_mult={lm:g}: {nt} tensors, {ne} parameters")
+
+
 def _eval_topk(cfg: TrainConfig) -> int:
     if cfg.eval_topk < 0:
         raise ValueError(f"eval_topk must be >= 0 (0 = off), got {cfg.eval_topk}")
@@ -373,6 +387,11 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
         if engine != "native" or isinstance(model, FrozenBackboneClassifier):
             raise ValueError("ema_decay > 0 needs the native training step (NativeTrainer); this run would use the "
                              f"{'frozen-backbone' if engine == 'native' else engine} engine, which keeps no weight EMA")
+    if has_param_groups(cfg.optim):
+        from ..models.wrappers import FrozenBackboneClassifier
+        if engine == "native" and isinstance(model, FrozenBackboneClassifier):
+            raise ValueError("parameter groups (optim.groups / norm_weight_decay / bias_weight_decay) are not "
+                             "supported by the frozen-backbone trainer this run would use: only the head trains")
     runner = _Native(cfg, model, train_dataset, dev, 0) if engine == "native" else _Autograd(cfg, model, train_dataset, dev)
     spe = runner.steps_per_epoch()
     total = cfg.max_steps or (parse_duration(cfg.duration, spe, cfg.batch_size) if cfg.duration else spe * cfg.epochs)
@@ -411,6 +430,8 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
                                "scheduler": cfg.sched.name, "num_gpus": ddist.get_world_size(), "engine": engine,
                                "zero_stage": cfg.zero.stage, "trainer": "dbx_amd", "ema_decay": cfg.ema_decay})
         _log(f"[train] engine={engine} world={ddist.get_world_size()} steps/epoch={spe} total_steps={total}")
+        if has_param_groups(cfg.optim):
+            _log_param_groups(runner)
         if cfg.grad_accum > 1 and cfg.checkpoint_dir and cfg.checkpoint_every and spe % cfg.grad_accum != 0:
             # (one iteration is one micro-batch; a checkpoint carries no accumulator)
             _log(f"[train] warning: steps/epoch={spe} is no multiple of grad_accum={cfg.grad_accum}: a run resumed "
