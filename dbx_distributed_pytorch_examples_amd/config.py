@@ -119,6 +119,29 @@ class DataConfig:
     shuffle: bool = True
     label_smoothing: float = 0.0
     cutmix_alpha: float = 0.0
+    # batch mixing and erasing (engine/mix.py; torchvision's ResNet-50 recipe: mixup 0.2, cutmix 1.0, erase 0.1)
+    mixup_alpha: float = 0.0           # MixUp: lam ~ Beta(a, a); 0 = off
+    mix_prob: float = 1.0              # a step mixes (MixUp or CutMix) with this probability
+    mix_switch_prob: float = 0.5       # with both alphas > 0: the share of mixing steps that use CutMix
+    erase_prob: float = 0.0            # random erasing: the share of samples that get a rectangle
+    erase_mode: str = "const"          # const (0 after normalisation) | pixel (N(0, 1) per pixel and channel)
+    erase_scale: Tuple[float, float] = (0.02, 1 / 3)   # rectangle area / image area
+    erase_ratio: Tuple[float, float] = (0.3, 3.3)      # rectangle height / width (log-uniform)
+
+
+def mix_options(d: DataConfig) -> Dict[str, Any]:
+    """The trainers' batch-mixing arguments from ``cfg.data``, validated (ValueError: a negative alpha, a
+    probability outside [0, 1], an unknown erase mode, a bad scale or ratio pair)."""
+    from .engine.mix import validate_mix
+    kw = dict(mixup_alpha=d.mixup_alpha, cutmix_alpha=d.cutmix_alpha, mix_prob=d.mix_prob,
+              mix_switch_prob=d.mix_switch_prob, erase_prob=d.erase_prob, erase_mode=d.erase_mode,
+              erase_scale=d.erase_scale, erase_ratio=d.erase_ratio)
+    validate_mix(**kw)
+    return kw
+
+
+def mixes_batches(d: DataConfig) -> bool:
+    return d.cutmix_alpha > 0 or d.mixup_alpha > 0 or d.erase_prob > 0
 
 
 @dataclass

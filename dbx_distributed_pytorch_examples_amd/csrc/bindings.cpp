@@ -89,6 +89,9 @@ int dbx_weight_prep(const float*, bf16*, const void*, int, hipStream_t);
 int dbx_weight_prep16(const bf16*, bf16*, const void*, int, hipStream_t);
 int dbx_augment_u8(const unsigned char*, bf16*, const float*, const unsigned char*, int, int, int, int, int, int, float,
                    float, float, float, float, float, const int*, const int*, hipStream_t);
+int dbx_augment_mix_u8(const unsigned char*, bf16*, const float*, const unsigned char*, int, int, int, int, int, int,
+                       float, float, float, float, float, float, const int*, const int*, const float*, const int*, int,
+                       unsigned long long, const int*, hipStream_t);
 int dbx_small_gemm(int, int, int, int, const dbx::GemmArgs*, hipStream_t);
 long long dbx_mnist_saved_bytes();
 int dbx_mnist_fwd(const float*, const float*, void*, float*, int, unsigned long long, unsigned, int, hipStream_t);
@@ -445,6 +448,17 @@ PYBIND11_MODULE(_C, m) {
                          P<const unsigned char*>(flip), N, Hin, Win, Cin, Ho, Wo, m0, m1, m2, s0, s1, s2,
                          P<const int*>(perm), P<const int*>(mixbox), S(st)),
           "augment_u8");
+  });
+  m.def("augment_mix_u8", [](uintptr_t in, uintptr_t out, uintptr_t boxes, uintptr_t flip, int N, int Hin, int Win,
+                             int Cin, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1, float s2,
+                             uintptr_t perm, uintptr_t mixbox, uintptr_t blend, uintptr_t erase, int pixel,
+                             unsigned long long seed, uintptr_t rng_offset, uintptr_t st) {
+    // the augment kernel with a MixUp blend and / or random erasing (nn_ops.hip augment_mix_u8_kernel)
+    check(dbx_augment_mix_u8(P<const unsigned char*>(in), P<bf16*>(out), P<const float*>(boxes),
+                             P<const unsigned char*>(flip), N, Hin, Win, Cin, Ho, Wo, m0, m1, m2, s0, s1, s2,
+                             P<const int*>(perm), P<const int*>(mixbox), P<const float*>(blend), P<const int*>(erase),
+                             pixel, seed, P<const int*>(rng_offset), S(st)),
+          "augment_mix_u8");
   });
   m.def("small_gemm", [](int ta, int tb, int out_f32, int drop, uintptr_t A, uintptr_t B, uintptr_t C, uintptr_t bias_f,
                          uintptr_t bias_h, int M, int N, int K, int lda, int ldb, int ldc, float alpha, int accumulate,

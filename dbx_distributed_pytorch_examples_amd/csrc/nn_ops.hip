@@ -17,6 +17,7 @@
 //   * SGD-momentum / Adam(W) over the flat fp32 master buffer, writing the bf16 compute copy.
 #include "common.h"
 #include "bn_fin.h"
+#include "philox.h"
 
 namespace dbx {
 
@@ -1329,6 +1330,145 @@ __global__ __launch_bounds__(256) void augment_u8_kernel(const unsigned char* __
   }
 }
 
+// The mixing form of the augment kernel (MixUp blend, random erasing; the CutMix paste as above).
+// With f_s(oy, ox) the normalised fp32 pixel of source sample s -- the plain kernel's expression, or
+// the erase value where (oy, ox) lies in erase[s] = (y0, y1, x0, x1), output coordinates --
+//   out[n] = f_perm[n]                              inside mixbox
+//          = bf16(w f_n + (1 - w) f_perm[n])        elsewhere, w = blend[0] read from memory
+// Erasing belongs to the source sample (torchvision / timm erase before they mix), so an erased
+// rectangle travels with a pasted or blended sample. w == 1 never reads the second sample (block-
+// uniform) and then, like an all-empty erase table, gives the plain kernel's bits. Erase value: 0
+// (pixel == 0), or one N(0, 1) draw per pixel and channel from the Philox counter
+// pix = (s Ho + oy) Wo + ox (Box-Muller on its four words, precise logf / sqrtf / cospif / sinpif):
+// a function of (seed, offset, source sample, position), so a copy of a sample carries its noise.
+// A row stages the two source rows of both samples (4 x 4096 B of LDS) when all four can be.
+struct AugMix {
+  const float* blend;         // fp32[1]; null: 1
+  const int* erase;           // int32 [N][4]; null: none
+  const int* rng_offset;      // int32[1] (pixel mode)
+  unsigned long long seed;
+  int pixel;
+};
+struct AugRow {  // what is uniform over one output row of one source sample
+  const unsigned char *g0, *g1;
+  float bx, sxs, wy;
+  int sn, ey0, ey1, ex0, ex1;
+  bool fl;
+};
+__device__ __forceinline__ AugRow aug_row(const unsigned char* __restrict__ in, const float* __restrict__ boxes,
+                                          const unsigned char* __restrict__ flip, const int* __restrict__ erase,
+                                          int sn, int oy, int Hin, int Win, int Cin, int Ho, int Wo) {
+  AugRow r;
+  const float by = boxes[4 * sn], bh = boxes[4 * sn + 2], bw = boxes[4 * sn + 3];
+  r.bx = boxes[4 * sn + 1];
+  r.fl = flip && flip[sn];
+  float sy = by + (oy + 0.5f) * bh / Ho - 0.5f;
+  sy = fminf(fmaxf(sy, 0.f), (float)(Hin - 1));
+  const int y0 = (int)sy, y1 = min(y0 + 1, Hin - 1);
+  r.wy = sy - y0;
+  r.g0 = in + ((size_t)sn * Hin + y0) * Win * Cin;
+  r.g1 = in + ((size_t)sn * Hin + y1) * Win * Cin;
+  r.sxs = bw / Wo;
+  r.sn = sn;
+  r.ey0 = r.ey1 = r.ex0 = r.ex1 = 0;
+  if (erase && oy >= erase[4 * sn] && oy < erase[4 * sn + 1]) {  // (an empty box erases no column either)
+    r.ey0 = erase[4 * sn]; r.ey1 = erase[4 * sn + 1]; r.ex0 = erase[4 * sn + 2]; r.ex1 = erase[4 * sn + 3];
+  }
+  return r;
+}
+
+__global__ __launch_bounds__(256) void augment_mix_u8_kernel(const unsigned char* __restrict__ in, bf16* __restrict__ out,
+                                                             const float* __restrict__ boxes,
+                                                             const unsigned char* __restrict__ flip, int N, int Hin,
+                                                             int Win, int Cin, int Ho, int Wo, float m0, float m1,
+                                                             float m2, float s0, float s1, float s2,
+                                                             const int* __restrict__ perm,
+                                                             const int* __restrict__ mixbox, const AugMix am) {
+  constexpr int kRowMax = 4096;
+  __shared__ __attribute__((aligned(16))) unsigned char srow[4][kRowMax];
+  const int my0 = mixbox ? mixbox[0] : 0, my1 = mixbox ? mixbox[1] : 0;
+  const int mx0 = mixbox ? mixbox[2] : 0, mx1 = mixbox ? mixbox[3] : 0;
+  const float i0 = 1.f / (255.f * s0), i1 = 1.f / (255.f * s1), i2 = 1.f / (255.f * s2);
+  const float w = (am.blend && perm) ? am.blend[0] : 1.f;
+  const bool blendrow = w != 1.f;  // grid-uniform
+  const unsigned roff = am.pixel ? (unsigned)am.rng_offset[0] : 0u;
+  for (int row = blockIdx.x; row < N * Ho; row += gridDim.x) {  // row = n * Ho + oy
+    const int n = row / Ho, oy = row - n * Ho;
+    const bool mixrow = perm && oy >= my0 && oy < my1 && mx0 < mx1;  // block-uniform
+    const bool two = mixrow || blendrow;                              // the row reads sample perm[n]
+    const AugRow A = aug_row(in, boxes, flip, am.erase, n, oy, Hin, Win, Cin, Ho, Wo);
+    const AugRow P = two ? aug_row(in, boxes, flip, am.erase, min(max(perm[n], 0), N - 1), oy, Hin, Win, Cin, Ho, Wo) : A;
+    const int rb = Win * Cin;
+    const bool staged = rb <= kRowMax && (rb & 15) == 0 &&
+                        (((size_t)A.g0 | (size_t)A.g1 | (size_t)P.g0 | (size_t)P.g1) & 15) == 0;  // block-uniform
+    if (staged) {
+      for (int o = threadIdx.x * 16; o < rb; o += blockDim.x * 16) {
+        *reinterpret_cast<u32x4*>(&srow[0][o]) = *reinterpret_cast<const u32x4*>(A.g0 + o);
+        *reinterpret_cast<u32x4*>(&srow[1][o]) = *reinterpret_cast<const u32x4*>(A.g1 + o);
+        if (two) {
+          *reinterpret_cast<u32x4*>(&srow[2][o]) = *reinterpret_cast<const u32x4*>(P.g0 + o);
+          *reinterpret_cast<u32x4*>(&srow[3][o]) = *reinterpret_cast<const u32x4*>(P.g1 + o);
+        }
+      }
+      __syncthreads();
+    }
+    // f_s at column ox: the erase value inside the sample's erase box, else the plain kernel's pixel
+    auto px = [&](const AugRow& r, const unsigned char* r0, const unsigned char* r1, int ox, float (&f)[3])
+                  __attribute__((always_inline)) {
+      if (ox >= r.ex0 && ox < r.ex1) {  // (the row test is in aug_row)
+        f[0] = f[1] = f[2] = 0.f;
+        if (am.pixel) {
+          unsigned u[4];
+          philox4x32_10(((unsigned long long)r.sn * Ho + oy) * Wo + ox, am.seed, roff, u);
+          const float k24 = 1.f / 16777216.f;
+          const float r01 = sqrtf(-2.f * logf((float)((u[0] >> 8) + 1u) * k24));
+          const float a01 = 2.f * ((float)(u[1] >> 8) * k24);
+          f[0] = r01 * cospif(a01);
+          f[1] = r01 * sinpif(a01);
+          f[2] = sqrtf(-2.f * logf((float)((u[2] >> 8) + 1u) * k24)) * cospif(2.f * ((float)(u[3] >> 8) * k24));
+        }
+        return;
+      }
+      const int oxx = r.fl ? (Wo - 1 - ox) : ox;
+      float sx = r.bx + (oxx + 0.5f) * r.sxs - 0.5f;
+      sx = fminf(fmaxf(sx, 0.f), (float)(Win - 1));
+      const int x0 = (int)sx, x1 = min(x0 + 1, Win - 1);
+      const float wx = sx - x0, wy = r.wy;
+      float v[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int cc = Cin == 1 ? 0 : c;
+        const float a = r0[x0 * Cin + cc], b = r0[x1 * Cin + cc];
+        const float d = r1[x0 * Cin + cc], e = r1[x1 * Cin + cc];
+        v[c] = (a * (1.f - wx) + b * wx) * (1.f - wy) + (d * (1.f - wx) + e * wx) * wy;  // 0..255
+      }
+      f[0] = v[0] * i0 - m0 / s0; f[1] = v[1] * i1 - m1 / s1; f[2] = v[2] * i2 - m2 / s2;
+    };
+    auto body = [&](const unsigned char* a0, const unsigned char* a1, const unsigned char* p0, const unsigned char* p1)
+                    __attribute__((always_inline)) {
+      for (int ox = threadIdx.x; ox < Wo; ox += blockDim.x) {
+        float f[3];
+        if (mixrow && ox >= mx0 && ox < mx1) {
+          px(P, p0, p1, ox, f);
+        } else {
+          px(A, a0, a1, ox, f);
+          if (blendrow) {
+            float q[3];
+            px(P, p0, p1, ox, q);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) f[c] = w * f[c] + (1.f - w) * q[c];
+          }
+        }
+        bf16x4 o = {(bf16)f[0], (bf16)f[1], (bf16)f[2], (bf16)0.f};
+        *reinterpret_cast<bf16x4*>(out + ((size_t)row * Wo + ox) * 4) = o;
+      }
+    };
+    if (staged) body(&srow[0][0], &srow[1][0], &srow[2][0], &srow[3][0]);  // LDS byte gathers
+    else body(A.g0, A.g1, P.g0, P.g1);
+    __syncthreads();  // srow reuse by the next row
+  }
+}
+
 // ----------------------------------------------------------------------------------------
 // Weight prep: fp32 KRSC master -> bf16 KRSC (fwd) and bf16 CRSK (dgrad) ; batched over layers
 // ----------------------------------------------------------------------------------------
@@ -1758,6 +1898,16 @@ extern "C" int dbx_augment_u8(const unsigned char* in, bf16* out, const float* b
                               float s2, const int* perm, const int* mixbox, hipStream_t st) {
   hipLaunchKernelGGL(augment_u8_kernel, dim3(N * Ho < 4096 ? N * Ho : 4096), dim3(Wo >= 256 ? 256 : ((Wo + 63) / 64) * 64), 0, st, in, out, boxes, flip, N,
                      Hin, Win, Cin, Ho, Wo, m0, m1, m2, s0, s1, s2, perm, mixbox);
+  RET_LAST;
+}
+extern "C" int dbx_augment_mix_u8(const unsigned char* in, bf16* out, const float* boxes, const unsigned char* flip,
+                                  int N, int Hin, int Win, int Cin, int Ho, int Wo, float m0, float m1, float m2, float s0,
+                                  float s1, float s2, const int* perm, const int* mixbox, const float* blend,
+                                  const int* erase, int pixel, unsigned long long seed, const int* rng_offset,
+                                  hipStream_t st) {
+  const AugMix am{blend, erase, rng_offset, seed, pixel};
+  hipLaunchKernelGGL(augment_mix_u8_kernel, dim3(N * Ho < 4096 ? N * Ho : 4096), dim3(Wo >= 256 ? 256 : ((Wo + 63) / 64) * 64), 0, st, in, out, boxes, flip, N,
+                     Hin, Win, Cin, Ho, Wo, m0, m1, m2, s0, s1, s2, perm, mixbox, am);
   RET_LAST;
 }
 extern "C" int dbx_weight_prep(const float* master, bf16* wbuf, const void* desc_dev, int nlayers, hipStream_t st) {

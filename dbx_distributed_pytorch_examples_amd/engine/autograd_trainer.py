@@ -162,6 +162,55 @@ def cutmix(x: torch.Tensor, y: torch.Tensor, num_classes: int, alpha: float, gen
     return x, lam * t + (1 - lam) * t[perm]
 
 
+def _beta(alpha: float, gen: Optional[torch.Generator] = None) -> float:
+    """One Beta(alpha, alpha) draw (two gamma draws when a generator is given)."""
+    if gen is None:
+        return torch.distributions.Beta(alpha, alpha).sample().item()
+    g = torch._standard_gamma(torch.full((2,), float(alpha), device=gen.device), generator=gen)
+    return (g[0] / g.sum().clamp_min(1e-30)).item()
+
+
+def mixup(x: torch.Tensor, y: torch.Tensor, num_classes: int, alpha: float, gen: Optional[torch.Generator] = None):
+    """MixUp (torchvision's ResNet-50 recipe: alpha 0.2): ``lam ~ Beta(alpha, alpha)``, every sample blended
+    with one of a permuted batch, ``lam x + (1 - lam) x[perm]``, one-hot targets mixed by the same weight --
+    the native step's semantics (K.augment_u8 ``blend``) on the float batch."""
+    lam = _beta(alpha, gen) if alpha > 0 else 1.0
+    perm = torch.randperm(x.shape[0], generator=gen, device=gen.device if gen is not None else "cpu").to(x.device)
+    t = F.one_hot(y, num_classes).float()
+    return lam * x + (1 - lam) * x[perm], lam * t + (1 - lam) * t[perm]
+
+
+def random_erase(x: torch.Tensor, p: float, scale=(0.02, 1 / 3), ratio=(0.3, 3.3), mode: str = "const",
+                 gen: Optional[torch.Generator] = None) -> torch.Tensor:
+    """Random erasing of a normalised float batch [B, C, H, W], torchvision's rule per sample: with
+    probability ``p`` up to 10 tries of ``area = H W U(scale)`` and a log-uniform aspect ratio; the first
+    with ``1 <= h < H`` and ``1 <= w < W`` is erased at a uniform position -- to 0 (``"const"``) or to N(0, 1)
+    noise per pixel and channel (``"pixel"``); a sample none of whose tries fits stays as it is. Applied
+    before any mixing, so the rectangle travels with its sample (the native step's semantics)."""
+    if mode not in ("const", "pixel"):
+        raise ValueError(f'mode must be "const" or "pixel", got {mode!r}')
+    B, C, H, W = x.shape
+    dev = gen.device if gen is not None else torch.device("cpu")
+    chosen = (torch.rand(B, generator=gen, device=dev) < p).nonzero().flatten().tolist()
+    if not chosen:
+        return x
+    x = x.clone()
+    l0, l1 = math.log(ratio[0]), math.log(ratio[1])
+    for i in chosen:
+        for _ in range(10):
+            u = torch.rand(2, generator=gen, device=dev).tolist()
+            area, ar = H * W * (scale[0] + (scale[1] - scale[0]) * u[0]), math.exp(l0 + (l1 - l0) * u[1])
+            h, w = int(round(math.sqrt(area * ar))), int(round(math.sqrt(area / ar)))
+            if not (1 <= h < H and 1 <= w < W):
+                continue
+            v = torch.rand(2, generator=gen, device=dev).tolist()
+            y0, x0 = min(int(v[0] * (H - h + 1)), H - h), min(int(v[1] * (W - w + 1)), W - w)
+            x[i, :, y0:y0 + h, x0:x0 + w] = 0.0 if mode == "const" else \
+                torch.randn(C, h, w, generator=gen, device=dev).to(x)
+            break
+    return x
+
+
 def soft_cross_entropy(logits: torch.Tensor, target: torch.Tensor, smoothing: float = 0.0) -> torch.Tensor:
     if smoothing:
         target = target * (1 - smoothing) + smoothing / target.shape[1]
@@ -173,7 +222,12 @@ class AutogradTrainer:
                  bucket_cap_mb: float = 64.0, channels_last: bool = True, zero_stage: int = 0,
                  cutmix_alpha: float = 0.0, grad_accum: int = 1, allreduce_dtype=torch.float32,
                  offload_optimizer: bool = False, offload_param: bool = False, bf16: bool = True,
-                 stage3: Optional[dict] = None):
+                 stage3: Optional[dict] = None, mixup_alpha: float = 0.0, mix_prob: float = 1.0,
+                 mix_switch_prob: float = 0.5, erase_prob: float = 0.0, erase_mode: str = "const",
+                 erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3)):
+        from .mix import validate_mix
+        validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, erase_mode, erase_scale,
+                     erase_ratio)
         self.dev = device
         self.bf16 = bool(bf16) and device.type == "cuda"  # autocast bf16 (DeepSpeed bf16.enabled)
         self.model = model.to(device)
@@ -195,6 +249,10 @@ class AutogradTrainer:
         self.o = optim
         self.smoothing = label_smoothing
         self.cutmix_alpha = cutmix_alpha
+        # MixUp, the per-step choice between it and CutMix, random erasing: the native step's rules (engine/mix.py)
+        self.mixup_alpha, self.mix_prob, self.mix_switch_prob = mixup_alpha, mix_prob, mix_switch_prob
+        self.erase_prob, self.erase_mode = erase_prob, erase_mode
+        self.erase_scale, self.erase_ratio = tuple(erase_scale), tuple(erase_ratio)
         self.grad_accum = max(1, grad_accum)
         self.num_classes = getattr(unwrap(model), "num_classes", None)
         self.zero = None
@@ -224,6 +282,18 @@ class AutogradTrainer:
             for g in self.opt.param_groups:
                 g["lr"] = lr * g.get("lr_mult", 1.0)
 
+    def _mix_kind(self) -> str:
+        """This step's mixing: none with probability 1 - mix_prob, else CutMix with probability
+        mix_switch_prob when both alphas are set (never both in one step)."""
+        cut, mix = self.cutmix_alpha > 0, self.mixup_alpha > 0
+        if not (cut or mix):
+            return "none"
+        if self.mix_prob < 1.0 and not torch.rand(()).item() < self.mix_prob:
+            return "none"
+        if cut and mix:
+            return "cutmix" if torch.rand(()).item() < self.mix_switch_prob else "mixup"
+        return "cutmix" if cut else "mixup"
+
     def _loss(self, out, x, y, target=None):
         m = unwrap(self.model)
         if hasattr(m, "loss") and callable(m.loss) and target is None:
@@ -242,8 +312,13 @@ class AutogradTrainer:
         if self.dev.type == "cuda" and x.dim() == 4:
             x = x.contiguous(memory_format=torch.channels_last)
         target = None
-        if self.cutmix_alpha > 0 and self.num_classes:
+        if self.erase_prob > 0 and x.dim() == 4:  # per sample, before any mixing
+            x = random_erase(x, self.erase_prob, self.erase_scale, self.erase_ratio, self.erase_mode)
+        kind = self._mix_kind() if self.num_classes else "none"
+        if kind == "cutmix":
             x, target = cutmix(x, y, self.num_classes, self.cutmix_alpha)
+        elif kind == "mixup":
+            x, target = mixup(x, y, self.num_classes, self.mixup_alpha)
         last_micro = (self.micro + 1) % self.grad_accum == 0
         ctx = self.ddp.no_sync() if not last_micro else _null()
         with ctx:

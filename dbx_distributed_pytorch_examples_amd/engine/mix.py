@@ -1,0 +1,136 @@
+"""Host-side sampling of the batch-mixing options of the native step: MixUp, the per-batch choice
+between MixUp and CutMix, and random erasing (torchvision's ResNet-50 reference recipe, timm's "ResNet
+strikes back"). Tiny numpy work per step; the device consumes what is sampled here through scalars
+and small tables (``ResNetProgram.enable_mix``), so a replayed graph follows it.
+
+Per step, from one ``numpy.random.Generator``, in this order:
+
+1. with probability ``1 - mix_prob`` no mixing (one ``random()``, drawn only when ``mix_prob < 1``);
+2. otherwise CutMix with probability ``mix_switch_prob`` when both alphas are > 0 (one ``random()``, drawn
+   only then); with one alpha > 0, that one;
+3. MixUp: ``lam ~ Beta(a, a)`` (``beta``), one batch permutation (``permutation``); the blend weight and the
+   CE weight are both ``lam``, the box is empty;
+   CutMix: ``lam ~ Beta(a, a)``, a box of area ``1 - lam`` at a uniform centre, clipped, ``lam`` re-derived
+   from the clipped area, one permutation (``beta``, ``integers``, ``integers``, ``permutation``: with only
+   ``cutmix_alpha`` set this is the whole sequence, the one the trainer has always drawn); blend weight 1;
+4. the erase boxes (:func:`sample_erase_boxes`), drawn only when ``erase_prob > 0``.
+
+MixUp and CutMix are never both applied in one step.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Optional, Tuple
+
+import numpy as np
+
+ERASE_MODES = ("const", "pixel")
+
+
+def validate_mix(mixup_alpha=0.0, cutmix_alpha=0.0, mix_prob=1.0, mix_switch_prob=0.5, erase_prob=0.0,
+                 erase_mode="const", erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3)) -> None:
+    """ValueError for a negative alpha, a probability outside [0, 1], an unknown mode or a bad range."""
+    for nm, v in (("mixup_alpha", mixup_alpha), ("cutmix_alpha", cutmix_alpha)):
+        if not (isinstance(v, (int, float)) and math.isfinite(v) and v >= 0):
+            raise ValueError(f"{nm} must be a finite number >= 0, got {v!r}")
+    for nm, v in (("mix_prob", mix_prob), ("mix_switch_prob", mix_switch_prob), ("erase_prob", erase_prob)):
+        if not (isinstance(v, (int, float)) and 0.0 <= v <= 1.0):
+            raise ValueError(f"{nm} must be a probability in [0, 1], got {v!r}")
+    if erase_mode not in ERASE_MODES:
+        raise ValueError(f"erase_mode must be one of {ERASE_MODES}, got {erase_mode!r}")
+    for nm, v, top in (("erase_scale", erase_scale, 1.0), ("erase_ratio", erase_ratio, math.inf)):
+        try:
+            lo, hi = (float(x) for x in v)
+        except (TypeError, ValueError):
+            raise ValueError(f"{nm} must be a (low, high) pair, got {v!r}") from None
+        if not (0.0 < lo <= hi <= top and math.isfinite(hi)):
+            raise ValueError(f"{nm} must satisfy 0 < low <= high{' <= 1' if top == 1.0 else ''}, got {v!r}")
+
+
+def sample_erase_boxes(rng: np.random.Generator, n: int, H: int, W: int, prob: float,
+                       scale=(0.02, 1 / 3), ratio=(0.3, 3.3), tries: int = 10) -> np.ndarray:
+    """torchvision's RandomErasing box rule for ``n`` samples at once: int32 [n, 4] (y0, y1, x0, x1), empty
+    (all zero) for a sample that is not erased. With probability ``prob`` a sample makes up to ``tries``
+    draws of ``area = H W U(scale)`` and a log-uniform aspect ratio, ``h = round(sqrt(area ar))``,
+    ``w = round(sqrt(area / ar))``; the first draw with ``1 <= h < H`` and ``1 <= w < W`` wins, at a uniform
+    position; a sample none of whose draws fits stays un-erased."""
+    chosen = rng.random(n) < prob
+    area = H * W * rng.uniform(scale[0], scale[1], (n, tries))
+    ar = np.exp(rng.uniform(math.log(ratio[0]), math.log(ratio[1]), (n, tries)))
+    h = np.rint(np.sqrt(area * ar)).astype(np.int64)
+    w = np.rint(np.sqrt(area / ar)).astype(np.int64)
+    fits = (h >= 1) & (h < H) & (w >= 1) & (w < W)
+    first = fits.argmax(axis=1)
+    rows = np.arange(n)
+    h, w = h[rows, first], w[rows, first]
+    ok = chosen & fits.any(axis=1)
+    y0 = np.floor(rng.random(n) * (H - h + 1)).astype(np.int64)
+    x0 = np.floor(rng.random(n) * (W - w + 1)).astype(np.int64)
+    y0, x0 = np.minimum(y0, np.maximum(H - h, 0)), np.minimum(x0, np.maximum(W - w, 0))
+    box = np.stack([y0, y0 + h, x0, x0 + w], axis=1)
+    return np.where(ok[:, None], box, 0).astype(np.int32)
+
+
+@dataclass
+class MixDraw:
+    """What one step uses: ``kind`` "none" | "mixup" | "cutmix"; ``lam`` the CE weight of the sample's own
+    label; ``blend`` the input blend weight (1 unless MixUp); ``perm`` int32 [N]; ``box`` (y0, y1, x0, x1);
+    ``erase`` int32 [N, 4] by source sample, or None when erasing is off."""
+    kind: str
+    lam: float
+    blend: float
+    perm: np.ndarray
+    box: Tuple[int, int, int, int]
+    erase: Optional[np.ndarray]
+
+
+class MixSampler:
+    def __init__(self, rng: np.random.Generator, N: int, H: int, W: int, *, mixup_alpha=0.0, cutmix_alpha=0.0,
+                 mix_prob=1.0, mix_switch_prob=0.5, erase_prob=0.0, erase_scale=(0.02, 1 / 3),
+                 erase_ratio=(0.3, 3.3)):
+        validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, "const", erase_scale,
+                     erase_ratio)
+        self.rng, self.N, self.H, self.W = rng, int(N), int(H), int(W)
+        self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+        self.mix_prob, self.mix_switch_prob = float(mix_prob), float(mix_switch_prob)
+        self.erase_prob = float(erase_prob)
+        self.erase_scale = tuple(float(v) for v in erase_scale)
+        self.erase_ratio = tuple(float(v) for v in erase_ratio)
+
+    def _kind(self) -> str:
+        r = self.rng
+        if self.mixup_alpha <= 0 and self.cutmix_alpha <= 0:
+            return "none"
+        if self.mix_prob < 1.0 and not r.random() < self.mix_prob:
+            return "none"
+        if self.mixup_alpha > 0 and self.cutmix_alpha > 0:
+            return "cutmix" if r.random() < self.mix_switch_prob else "mixup"
+        return "cutmix" if self.cutmix_alpha > 0 else "mixup"
+
+    def sample(self) -> MixDraw:
+        r, N, H, W = self.rng, self.N, self.H, self.W
+        kind = self._kind()
+        lam, blend, box = 1.0, 1.0, (0, 0, 0, 0)
+        if kind == "mixup":
+            # (the fp32 value the device scalars hold, so the blend and the CE weight are one number)
+            lam = blend = float(np.float32(r.beta(self.mixup_alpha, self.mixup_alpha)))
+            perm = r.permutation(N).astype("int32")
+        elif kind == "cutmix":
+            # lam ~ Beta(a, a); box of area (1 - lam) at a uniform centre, clipped; lam re-derived from
+            # the clipped area (Composer's CutMix); one permutation of the batch
+            lam = float(r.beta(self.cutmix_alpha, self.cutmix_alpha))
+            cut = (1.0 - lam) ** 0.5
+            ch, cw = int(H * cut), int(W * cut)
+            cy, cx = int(r.integers(0, H)), int(r.integers(0, W))
+            y0, y1 = min(max(cy - ch // 2, 0), H), min(max(cy + ch // 2, 0), H)
+            x0, x1 = min(max(cx - cw // 2, 0), W), min(max(cx + cw // 2, 0), W)
+            lam = 1.0 - (y1 - y0) * (x1 - x0) / float(H * W)
+            box = (y0, y1, x0, x1)
+            perm = r.permutation(N).astype("int32")
+        else:
+            perm = np.arange(N, dtype="int32")
+        erase = None
+        if self.erase_prob > 0:
+            erase = sample_erase_boxes(r, N, H, W, self.erase_prob, self.erase_scale, self.erase_ratio)
+        return MixDraw(kind, lam, blend, perm, box, erase)

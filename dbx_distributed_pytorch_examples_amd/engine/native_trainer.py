@@ -37,6 +37,7 @@ from ..parallel.dist import host_sync_for_gloo
 from ..utils import debug as _debug
 from ..utils.profiling import PhaseTimer
 from .hyper import DeviceHyper
+from .mix import MixDraw, MixSampler, validate_mix
 from .program import ResNetProgram, release_dead_graphs
 
 
@@ -78,7 +79,11 @@ class NativeTrainer:
                  process_group=None, src_hw: Optional[Tuple[int, int]] = None, mean=None, std=None,
                  zero_stage: int = 0, cutmix_alpha: float = 0.0, seed: int = 0,
                  engine: Optional[EngineConfig] = None, grad_accum: int = 1, ema_decay: float = 0.0,
-                 ema_warmup: bool = False):
+                 ema_warmup: bool = False, mixup_alpha: float = 0.0, mix_prob: float = 1.0,
+                 mix_switch_prob: float = 0.5, erase_prob: float = 0.0, erase_mode: str = "const",
+                 erase_scale: Tuple[float, float] = (0.02, 1 / 3), erase_ratio: Tuple[float, float] = (0.3, 3.3)):
+        validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, erase_mode, erase_scale,
+                     erase_ratio)
         self.dev = device
         self.cfg = cfg = engine if engine is not None else EngineConfig.current()
         optim = optim or OptimConfig()
@@ -113,11 +118,21 @@ class NativeTrainer:
         # CutMix (Composer's CutMix(alpha), `03_composer/01_cifar_composer_resnet.ipynb:430`): per step a
         # batch permutation and one box are sampled here (host, tiny) and applied on the device by the
         # augment kernel (paste) and the CE kernel (mixed soft targets) inside the captured step
+        # MixUp blends the batch with its permutation instead (weight lam ~ Beta(a, a), the CE's lam too);
+        # with both alphas set, each step takes one of the two. Random erasing replaces one rectangle per
+        # chosen sample before any mixing. Sampling: engine/mix.py; the kernel: K.augment_u8.
         self.cutmix_alpha = float(cutmix_alpha)
-        self._rng = __import__("numpy").random.default_rng(seed + 7919 * (dist.get_rank(process_group)
-                                                                          if self.world > 1 else 0))
-        if self.cutmix_alpha > 0:
-            self.prog.enable_cutmix()
+        self.mixup_alpha, self.erase_prob, self.erase_mode = float(mixup_alpha), float(erase_prob), erase_mode
+        rng_seed = seed + 7919 * (dist.get_rank(process_group) if self.world > 1 else 0)
+        self._rng = __import__("numpy").random.default_rng(rng_seed)
+        self.last_mix: Optional[MixDraw] = None  # what the last step used
+        self._mix, self._mix_ring, self._mix_slot = None, None, 0
+        if self.cutmix_alpha > 0 or self.mixup_alpha > 0 or self.erase_prob > 0:
+            self.prog.enable_mix(blend=self.mixup_alpha > 0, erase=self.erase_prob > 0, erase_mode=erase_mode,
+                                 seed=rng_seed)
+            self._mix = MixSampler(self._rng, self.prog.N, self.prog.H, self.prog.W, mixup_alpha=mixup_alpha,
+                                   cutmix_alpha=cutmix_alpha, mix_prob=mix_prob, mix_switch_prob=mix_switch_prob,
+                                   erase_prob=erase_prob, erase_scale=erase_scale, erase_ratio=erase_ratio)
         n = self.prog.n_params
         self.mom = torch.zeros(n, device=device)
         self.mom2 = torch.zeros(n, device=device) if optim.name in ("adam", "adamw", "lamb") else None
@@ -655,27 +670,52 @@ class NativeTrainer:
                 chunk.copy_(buf)
             pos = end
 
-    def _sample_cutmix(self):
-        """lam ~ Beta(a, a); box of area (1 - lam) at a uniform centre, clipped; lam re-derived from
-        the clipped area (Composer's CutMix); one permutation of the batch."""
-        p, r = self.prog, self._rng
-        H, W = p.H, p.W
-        lam = float(r.beta(self.cutmix_alpha, self.cutmix_alpha))
-        cut = (1.0 - lam) ** 0.5
-        ch, cw = int(H * cut), int(W * cut)
-        cy, cx = int(r.integers(0, H)), int(r.integers(0, W))
-        y0, y1 = min(max(cy - ch // 2, 0), H), min(max(cy + ch // 2, 0), H)
-        x0, x1 = min(max(cx - cw // 2, 0), W), min(max(cx + cw // 2, 0), W)
-        lam = 1.0 - (y1 - y0) * (x1 - x0) / float(H * W)
-        perm = torch.from_numpy(r.permutation(p.N).astype("int32"))
-        box = torch.tensor([y0, y1, x0, x1], dtype=torch.int32)
-        lamt = torch.tensor([lam], dtype=torch.float32)
+    def _sample_mix(self):
+        """This step's mixing (engine/mix.py: none / MixUp / CutMix, erase boxes) from the trainer's
+        generator, written to the program's device scalars and tables through pinned buffers. With only
+        ``cutmix_alpha`` set: the draws and the three copies the trainer has always made."""
+        p = self.prog
+        d = self.last_mix = self._mix.sample()
+        if p.mix_arena is not None:
+            # the mixing kernel's state is one arena (ResNetProgram.enable_mix): one copy per step from a
+            # small pinned ring whose slot is rewritten only after its previous copy completed (engine/hyper.py:
+            # a pinned allocation per step is enough host work to stall a ~1 ms step)
+            N = p.N
+            if self._mix_ring is None:
+                cuda = self.dev.type == "cuda"
+                self._mix_ring = [(torch.zeros(5 * N + 6, dtype=torch.int32).pin_memory() if cuda
+                                   else torch.zeros(5 * N + 6, dtype=torch.int32),
+                                   torch.cuda.Event() if cuda else None) for _ in range(4)]
+            buf, ev = self._mix_ring[self._mix_slot]
+            self._mix_slot = (self._mix_slot + 1) % len(self._mix_ring)
+            if ev is not None:
+                ev.synchronize()  # (a no-op for a fresh event)
+            h = buf.numpy()
+            h[:N] = d.perm
+            h[N:N + 4] = d.box
+            h[N + 4:N + 6].view("float32")[:] = (d.lam, d.blend)
+            h[N + 6:] = d.erase.reshape(-1) if d.erase is not None else 0
+            p.mix_arena.copy_(buf, non_blocking=True)
+            if ev is not None:
+                ev.record()
+            return
+        host = [(p.mix_perm, torch.from_numpy(d.perm)),
+                (p.mix_box, torch.tensor(d.box, dtype=torch.int32)),
+                (p.mix_lam, torch.tensor([d.lam], dtype=torch.float32))]
         if self.dev.type == "cuda":
-            perm, box, lamt = perm.pin_memory(), box.pin_memory(), lamt.pin_memory()
-        self._mix_host = (perm, box, lamt)  # keep the pinned sources alive until the copies ran
-        p.mix_perm.copy_(perm, non_blocking=True)
-        p.mix_box.copy_(box, non_blocking=True)
-        p.mix_lam.copy_(lamt, non_blocking=True)
+            host = [(dst, src.pin_memory()) for dst, src in host]
+        self._mix_host = host  # keep the pinned sources alive until the copies ran
+        for dst, src in host:
+            dst.copy_(src, non_blocking=True)
+
+    def mix_summary(self) -> dict:
+        """The batch-mixing settings, for logging."""
+        m = self._mix
+        return {"mixup_alpha": self.mixup_alpha, "cutmix_alpha": self.cutmix_alpha,
+                "mix_prob": m.mix_prob if m else 1.0, "mix_switch_prob": m.mix_switch_prob if m else 0.5,
+                "erase_prob": self.erase_prob, "erase_mode": self.erase_mode,
+                "erase_scale": m.erase_scale if m else None, "erase_ratio": m.erase_ratio if m else None,
+                "kernel": "augment_mix_u8" if self.prog.mix_blend is not None else "augment_u8"}
 
     def _set_hyper(self, boundary: bool = True):
         o = self.opt
@@ -833,8 +873,8 @@ class NativeTrainer:
             p.boxes.copy_(boxes, non_blocking=True)
         if flips is not None:
             p.flip.copy_(flips, non_blocking=True)
-        if self.cutmix_alpha > 0:
-            self._sample_cutmix()
+        if self._mix is not None:
+            self._sample_mix()
         # gradient accumulation: every call but the window's last is a micro-step
         boundary = self.micro == self.k - 1
         self._set_hyper(boundary)

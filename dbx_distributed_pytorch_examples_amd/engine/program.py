@@ -654,6 +654,10 @@ class ResNetProgram:
         # augment kernel (box paste) and the CE kernel (mixed soft targets)
         self.cutmix = False
         self.mix_perm = self.mix_box = self.mix_lam = self.labels2 = None
+        # MixUp / random erasing (enable_mix): the blend weight, the per-sample erase boxes and the
+        # Philox offset of the "pixel" erase noise, consumed by the mixing form of the augment kernel
+        self.mix_blend = self.erase_box = self.erase_off = self._erase_ctr = self.mix_arena = None
+        self.erase_mode, self.erase_seed = "const", 0
 
     def _pack_wdesc(self, descs) -> torch.Tensor:
         return K.pack_wdesc(descs, self.dev)
@@ -664,6 +668,8 @@ class ResNetProgram:
         extra = [(self.stats_region.data_ptr(), 0, -3, self.stats_region.numel(), 0, 0)]
         if self.nbt.numel():
             extra.append((self.nbt.data_ptr(), 0, -4, self.nbt.numel(), 0, 0))
+        if self._erase_ctr is not None:  # the erase noise's Philox offset: + 1 per step, on the device
+            extra.append((self._erase_ctr.data_ptr(), 0, -4, 1, 0, 0))
         self.wdesc_step = self._pack_wdesc(self._wdescs + extra) if self.dev.type == "cuda" else None
         self.n_wdesc_step = len(self._wdescs) + len(extra)
         self._stats_zeroed = False
@@ -718,7 +724,37 @@ class ResNetProgram:
     def _fused_fin(self, bn) -> bool:
         return self.fuse_fin and bn.fin_f is not None
 
+    def enable_mix(self, blend: bool = False, erase: bool = False, erase_mode: str = "const", seed: int = 0) -> None:
+        """Batch mixing and erasing in the training-mode input kernel: the CutMix state, plus -- with
+        ``blend`` (MixUp) or ``erase`` -- the blend weight ``mix_blend`` (fp32[1], 1 = no blend), the
+        per-source-sample boxes ``erase_box`` (int32 [N, 4], empty = not erased) and the Philox offset
+        ``erase_off`` of the "pixel" erase noise, which the step's weight-prep launch advances by one.
+        The trainer writes them per step; evaluation never reads them."""
+        if erase_mode not in ("const", "pixel"):
+            raise ValueError(f'erase_mode must be "const" or "pixel", got {erase_mode!r}')
+        dev = self.dev
+        self.enable_cutmix()
+        if not (blend or erase):
+            return
+        # one int32 arena [perm N | box 4 | lam 1 | blend 1 | erase 4 N] that the trainer refreshes with ONE
+        # host-to-device copy per step; the tensors the kernels take are views of it (lam / blend: fp32 bits)
+        N = self.N
+        self.mix_arena = a = torch.zeros(5 * N + 6, device=dev, dtype=torch.int32)
+        a[:N] = self.mix_perm
+        self.mix_perm, self.mix_box = a[:N], a[N:N + 4]
+        self.mix_lam, self.mix_blend = a[N + 4:N + 5].view(torch.float32), a[N + 5:N + 6].view(torch.float32)
+        self.mix_lam.fill_(1.0)
+        self.mix_blend.fill_(1.0)
+        self.erase_box = a[N + 6:].view(N, 4)
+        self.erase_mode, self.erase_seed = erase_mode, int(seed) & (2 ** 64 - 1)
+        # an int64 counter (the weight-prep launch's counter entry adds 1 to int64s); the kernel reads
+        # its low word, an int32 that wraps
+        self._erase_ctr = torch.zeros(1, device=dev, dtype=torch.int64)
+        self.erase_off = self._erase_ctr.view(torch.int32)[0:1]
+        self._pack_step_descs()
+
     def enable_cutmix(self) -> None:
+        """The CutMix state alone (:meth:`enable_mix` without a blend or erasing)."""
         dev = self.dev
         self.cutmix = True
         self.mix_perm = torch.arange(self.N, device=dev, dtype=torch.int32)
@@ -743,6 +779,8 @@ class ResNetProgram:
         K.weight_prep(src, self.w16buf, self.wdesc, self.n_wdesc)
         if step:
             self.nbt.add_(1)
+            if self._erase_ctr is not None:
+                self._erase_ctr.add_(1)
 
     def bn_param_blocks(self) -> List[Tuple[int, int]]:
         """Contiguous [lo, hi) blocks of the flat buffer holding BatchNorm affine parameters (read in
@@ -763,8 +801,13 @@ class ResNetProgram:
         if self.norm_mean and len(mean) == 1:
             mean, std = mean * 3, std * 3
         mix = self.cutmix and self.training
-        K.augment_u8(self.img_u8, self.x4, self.boxes, mean, std, self.flip if flip is None else flip,
-                     perm=self.mix_perm if mix else None, mixbox=self.mix_box if mix else None)
+        if mix and self.mix_blend is not None:
+            K.augment_u8(self.img_u8, self.x4, self.boxes, mean, std, self.flip if flip is None else flip,
+                         perm=self.mix_perm, mixbox=self.mix_box, blend=self.mix_blend, erase=self.erase_box,
+                         erase_mode=self.erase_mode, erase_rng=(self.erase_seed, self.erase_off))
+        else:
+            K.augment_u8(self.img_u8, self.x4, self.boxes, mean, std, self.flip if flip is None else flip,
+                         perm=self.mix_perm if mix else None, mixbox=self.mix_box if mix else None)
         if mix:  # the pasted samples' labels (device gather, inside the captured step)
             torch.index_select(self.labels, 0, self.mix_perm.long(), out=self.labels2)
 

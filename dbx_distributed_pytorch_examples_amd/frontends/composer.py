@@ -2,8 +2,8 @@
 
 ``Trainer(model, optimizers, train_dataloader, eval_dataloader, max_duration="2ep",
 algorithms=[LabelSmoothing(0.1), CutMix(1.0), ChannelsLast()], loggers=[MLFlowLogger(...)]).fit()``.
-Algorithms map onto the engine: label smoothing -> the CE target, CutMix -> the batch-mixing step
-(soft-label CE), ChannelsLast -> a no-op marker (every GPU path here is NHWC end to end, K19).
+Algorithms map onto the engine: label smoothing -> the CE target, CutMix / MixUp -> the batch-mixing step
+(soft-label CE; with both, each step takes one of the two), ChannelsLast -> a no-op marker (every GPU path here is NHWC end to end, K19).
 The model follows Composer's ``forward(batch)`` / ``loss(outputs, batch)`` convention
 (``models.ComposerResNet50``); plain modules work too.
 
@@ -38,6 +38,13 @@ class LabelSmoothing(Algorithm):
 
 class CutMix(Algorithm):
     def __init__(self, alpha: float = 1.0, num_classes: Optional[int] = None):
+        self.alpha, self.num_classes = alpha, num_classes
+
+
+class MixUp(Algorithm):
+    """Composer's ``MixUp(alpha)``: the batch blended with a permutation of itself, soft targets."""
+
+    def __init__(self, alpha: float = 0.2, num_classes: Optional[int] = None):
         self.alpha, self.num_classes = alpha, num_classes
 
 
@@ -83,6 +90,7 @@ class Trainer:
         model = self._maybe_native(model, train_dataloader)
         smoothing = next((a.smoothing for a in algorithms if isinstance(a, LabelSmoothing)), 0.0)
         cut = next((a for a in algorithms if isinstance(a, CutMix)), None)
+        mix = next((a for a in algorithms if isinstance(a, MixUp)), None)
         oc = OptimizerConfig(name="adam", lr=1e-4, weight_decay=0.0)
         if optimizers is not None:
             g = optimizers.param_groups[0]
@@ -91,9 +99,10 @@ class Trainer:
                                  momentum=g.get("momentum", 0.9), weight_decay=g.get("weight_decay", 0.0),
                                  betas=tuple(g.get("betas", (0.9, 0.999))), eps=g.get("eps", 1e-8))
         self.tr = AutogradTrainer(model, self.info.device, oc, label_smoothing=smoothing,
-                                  cutmix_alpha=cut.alpha if cut else 0.0)
-        if cut and cut.num_classes:
-            self.tr.num_classes = cut.num_classes
+                                  cutmix_alpha=cut.alpha if cut else 0.0, mixup_alpha=mix.alpha if mix else 0.0)
+        for a in (cut, mix):
+            if a and a.num_classes:
+                self.tr.num_classes = a.num_classes
         self.train_dl, self.eval_dl = train_dataloader, eval_dataloader
         self.max_duration = max_duration
         self.loggers = list(loggers)

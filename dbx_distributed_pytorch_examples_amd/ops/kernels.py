@@ -1650,11 +1650,22 @@ def normalize_u8(img, out, mean, std, flip=None):
 
 
 @_dispatch
-def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None):
+def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *, blend=None, erase=None,
+               erase_mode="const", erase_rng=None):
     """uint8 NHWC -> bf16 NHWC4: per-sample crop box [N,4] (y0, x0, h, w; fp32) bilinear-resized to
     out's H x W, optional flip [N] uint8, normalised. CutMix: ``perm`` [N] int32 + ``mixbox`` int32
     [y0, y1, x0, x1] (output coordinates; empty box = no mixing) paste sample perm[n]'s augmented
-    pixels into the box."""
+    pixels into the box.
+
+    MixUp: ``blend`` (fp32[1] device tensor w, read at run time; needs ``perm``, ``mixbox`` may then be
+    None = an empty box): outside the box ``out[n] = bf16(w f_n + (1 - w) f_perm[n])`` in fp32; w == 1 reads
+    no second sample and gives the bits of the call without ``blend``. Random erasing: ``erase`` int32
+    [N,4] (y0, y1, x0, x1) in output coordinates, indexed by SOURCE sample (y1 <= y0 or x1 <= x0: not
+    erased) -- the rectangle replaces the sample's pixels before any paste or blend, so it travels with
+    the sample. ``erase_mode`` "const": exactly 0 (normalised space); "pixel": N(0, 1) per pixel and
+    channel from Philox counter (s Ho + oy) Wo + ox with ``erase_rng = (seed, offset int32[1] device
+    tensor)`` (see :func:`reference.erase_noise`). The pad channel stays 0. Calls without ``blend`` and
+    ``erase`` run the plain kernel."""
     N, Hin, Win, Cin = img.shape
     _, Ho, Wo, C4 = out.shape
     _chk(img, torch.uint8, "img")
@@ -1662,14 +1673,26 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None):
     _chk(boxes, torch.float32, "boxes", N * 4)
     if flip is not None:
         _chk(flip, torch.uint8, "flip", N)
-    if (perm is None) != (mixbox is None):
-        raise ValueError("perm and mixbox come together")
+    seed, offset = _ref.check_augment_mix(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
     if perm is not None:
         _chk(perm, torch.int32, "perm", N)
+    if mixbox is not None:
         _chk(mixbox, torch.int32, "mixbox", 4)
-    C().augment_u8(img.data_ptr(), out.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Cin, Ho, Wo,
-                   float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]), float(std[2]),
-                   _p(perm), _p(mixbox), stream_ptr())
+    norm = (float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]), float(std[2]))
+    if blend is None and erase is None:
+        C().augment_u8(img.data_ptr(), out.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Cin, Ho, Wo,
+                       *norm, _p(perm), _p(mixbox), stream_ptr())
+        return
+    if blend is not None:
+        _chk(blend, torch.float32, "blend", 1)
+    pixel = erase is not None and erase_mode == "pixel"
+    if erase is not None:
+        _chk(erase, torch.int32, "erase", N * 4)
+    if pixel:
+        _chk(offset, torch.int32, "erase_rng offset", 1)
+    C().augment_mix_u8(img.data_ptr(), out.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Cin, Ho, Wo,
+                       *norm, _p(perm), _p(mixbox), _p(blend), _p(erase), int(pixel), seed if pixel else 0,
+                       _p(offset) if pixel else 0, stream_ptr())
 
 
 def pack_wdesc(descs, device) -> torch.Tensor:

@@ -687,7 +687,93 @@ def normalize_u8(img, out, mean, std, flip=None):
     out.copy_(o.bfloat16())
 
 
-def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None):
+ERASE_MODES = ("const", "pixel")
+
+
+def check_augment_mix(N, perm, mixbox, blend, erase, erase_mode, erase_rng):
+    """The argument rules of ``augment_u8``'s mixing options (shared by the kernel wrapper and the CPU
+    path); returns ``(seed, offset)`` of the pixel mode, else ``(None, None)``."""
+    if erase_mode not in ERASE_MODES:
+        raise ValueError(f"erase_mode must be one of {ERASE_MODES}, got {erase_mode!r}")
+    if blend is not None and perm is None:
+        raise ValueError("blend needs perm (the sample each one is blended with)")
+    if blend is None and (perm is None) != (mixbox is None):
+        raise ValueError("perm and mixbox come together")
+    if mixbox is not None and perm is None:
+        raise ValueError("mixbox needs perm")
+    for t, dt, nm, n in ((perm, torch.int32, "perm", N), (mixbox, torch.int32, "mixbox", 4),
+                         (blend, torch.float32, "blend", 1), (erase, torch.int32, "erase", 4 * N)):
+        if t is None:
+            continue
+        if t.dtype != dt:
+            raise TypeError(f"{nm}: expected {dt}, got {t.dtype}")
+        if t.numel() != n:
+            raise ValueError(f"{nm}: expected {n} elements, got {t.numel()} (shape {tuple(t.shape)})")
+    if erase is None or erase_mode != "pixel":
+        return None, None
+    if erase_rng is None:
+        raise ValueError('erase_mode "pixel" needs erase_rng = (seed, offset int32[1] tensor)')
+    seed, offset = erase_rng
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"erase_rng: the seed must fit 64 bits, got {seed}")
+    if not isinstance(offset, torch.Tensor) or offset.dtype != torch.int32 or offset.numel() != 1:
+        raise TypeError("erase_rng: the offset is an int32[1] tensor (read at run time)")
+    return seed, offset
+
+
+def erase_noise(seed: int, offset: int, pix) -> torch.Tensor:
+    """The "pixel" erase values [len(pix), 3] (fp32) of the Philox counters ``pix = (s Ho + oy) Wo + ox``:
+    with words w0..w3 of counter pix, u(w) = ((w >> 8) + 1) 2^-24 in (0, 1], g(w) = (w >> 8) 2^-24 in [0, 1):
+    z0 = sqrt(-2 ln u(w0)) cos(2 pi g(w1)), z1 = the same radius times sin(2 pi g(w1)),
+    z2 = sqrt(-2 ln u(w2)) cos(2 pi g(w3)). Evaluated in float64 and rounded once."""
+    import numpy as np
+    pix = np.asarray(pix, dtype=np.uint64)
+    w = [philox_u32(pix * np.uint64(4) + np.uint64(k), seed, offset) for k in range(4)]
+
+    def u(x):
+        return ((x >> np.uint64(8)) + np.uint64(1)).astype(np.float64) * 2.0 ** -24
+
+    def g(x):
+        return (x >> np.uint64(8)).astype(np.float64) * 2.0 ** -24
+    r01, a01 = np.sqrt(-2.0 * np.log(u(w[0]))), 2.0 * np.pi * g(w[1])
+    z = np.stack([r01 * np.cos(a01), r01 * np.sin(a01),
+                  np.sqrt(-2.0 * np.log(u(w[2]))) * np.cos(2.0 * np.pi * g(w[3]))], axis=-1)
+    return torch.from_numpy(z.astype(np.float32))
+
+
+def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *, blend=None, erase=None,
+               erase_mode="const", erase_rng=None):
+    seed, offset = check_augment_mix(img.shape[0], perm, mixbox, blend, erase, erase_mode, erase_rng)
+    if blend is not None or erase is not None:
+        # f_s per source sample (erased where erase[s] says so), then the blend, then the paste
+        f = _augment_f32(img, out, boxes, mean, std, flip)
+        _, Ho, Wo, _ = out.shape
+        if erase is not None:
+            off = int(offset.reshape(-1)[0]) if offset is not None else 0
+            for s, (y0, y1, x0, x1) in enumerate(erase.reshape(-1, 4).tolist()):
+                y0, y1, x0, x1 = max(y0, 0), min(y1, Ho), max(x0, 0), min(x1, Wo)  # (the kernel tests positions)
+                if y0 >= y1 or x0 >= x1:
+                    continue
+                f[s, y0:y1, x0:x1] = 0.0
+                if erase_mode == "pixel":
+                    oy = torch.arange(y0, y1).view(-1, 1)
+                    ox = torch.arange(x0, x1).view(1, -1)
+                    pix = ((s * Ho + oy) * Wo + ox).reshape(-1).numpy()
+                    f[s, y0:y1, x0:x1, :3] = erase_noise(seed, off, pix).view(y1 - y0, x1 - x0, 3).to(f.device)
+        res = f
+        if perm is not None:
+            fp = f[perm.long()]
+            w = blend.reshape(-1)[0] if blend is not None else None
+            if w is not None and float(w) != 1.0:
+                res = w * f + (1.0 - w) * fp  # fp32 throughout
+            if mixbox is not None:
+                y0, y1, x0, x1 = (int(v) for v in mixbox.tolist())
+                if y0 < y1 and x0 < x1:
+                    res = res.clone()
+                    res[:, y0:y1, x0:x1] = fp[:, y0:y1, x0:x1]
+        out.copy_(res.bfloat16())
+        return
     if perm is not None:  # CutMix: the augmented batch, then the box pasted from sample perm[n]
         augment_u8(img, out, boxes, mean, std, flip)
         y0, y1, x0, x1 = (int(v) for v in mixbox.tolist())
@@ -695,6 +781,11 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None):
             src = out.clone()
             out[:, y0:y1, x0:x1] = src[perm.long()][:, y0:y1, x0:x1]
         return
+    out.copy_(_augment_f32(img, out, boxes, mean, std, flip).bfloat16())
+
+
+def _augment_f32(img, out, boxes, mean, std, flip=None):
+    """The normalised fp32 batch [N, Ho, Wo, 4] (pad channel 0) of ``augment_u8`` before its rounding."""
     N, Hin, Win, Cin = img.shape
     _, Ho, Wo, _ = out.shape
     dev = img.device
@@ -717,7 +808,7 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None):
         im = im[..., :3]
         v = ((im[y0][:, x0] * (1 - wx) + im[y0][:, x1] * wx) * (1 - wy) + (im[y1][:, x0] * (1 - wx) + im[y1][:, x1] * wx) * wy)
         res[n, ..., :3] = (v / 255.0 - m) / s
-    out.copy_(res.bfloat16())
+    return res
 
 
 def weight_prep(master, wbuf, desc_dev, nlayers):

@@ -35,7 +35,8 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from ..config import TrainConfig, from_deepspeed, has_param_groups, parse_duration, to_dict
+from ..config import (TrainConfig, from_deepspeed, has_param_groups, mix_options, mixes_batches, parse_duration,
+                      to_dict)
 from ..models import build_model
 from ..parallel import dist as ddist
 from ..parallel.sampler import ShardSampler
@@ -146,8 +147,8 @@ class _Native:
                                     label_smoothing=cfg.data.label_smoothing, use_graphs=cfg.graphs,
                                     bucket_cap_mb=cfg.bucket_cap_mb, allreduce_dtype=ar,
                                     src_hw=(h, w), mean=mean, std=std, zero_stage=cfg.zero.stage,
-                                    cutmix_alpha=cfg.data.cutmix_alpha, seed=cfg.seed,
-                                    grad_accum=cfg.grad_accum, ema_decay=cfg.ema_decay, ema_warmup=cfg.ema_warmup)
+                                    seed=cfg.seed, grad_accum=cfg.grad_accum, ema_decay=cfg.ema_decay,
+                                    ema_warmup=cfg.ema_warmup, **mix_options(cfg.data))
         self.ema_eval = bool(cfg.ema_eval)
         self.eval_topk, self.eval_graph = _eval_topk(cfg), bool(cfg.eval_graph)
         if not cfg.data.augment:
@@ -243,7 +244,7 @@ class _Autograd:
         from ..engine.autograd_trainer import AutogradTrainer
         self.tr = AutogradTrainer(model, dev, cfg.optim, label_smoothing=cfg.data.label_smoothing,
                                   bucket_cap_mb=cfg.bucket_cap_mb, zero_stage=cfg.zero.stage,
-                                  cutmix_alpha=cfg.data.cutmix_alpha, grad_accum=cfg.grad_accum,
+                                  grad_accum=cfg.grad_accum, **mix_options(cfg.data),
                                   offload_optimizer=cfg.zero.offload_optimizer, offload_param=cfg.zero.offload_param,
                                   bf16=cfg.precision == "bf16", stage3=_stage3_kw(cfg.zero),
                                   allreduce_dtype=torch.bfloat16 if cfg.allreduce_dtype == "bf16" else torch.float32)
@@ -312,7 +313,7 @@ def _pick_engine(cfg: TrainConfig, model, ds, dev) -> str:
     # (gradient accumulation: the native trainer's micro-steps; the frozen-backbone trainer has none)
     if dev.type == "cuda" and (supports(model) or frozen) and _uint8_source(ds) \
             and (cfg.grad_accum == 1 or not frozen) \
-            and (cfg.data.cutmix_alpha == 0 or not frozen):  # CutMix: native box paste + soft-target CE
+            and (not mixes_batches(cfg.data) or not frozen):  # CutMix / MixUp / erasing: the native input kernel
         return "native"
     return "autograd"
 
@@ -379,6 +380,7 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
         else:
             train_dataset = build_dataset(d.dataset, d.root, True, None, d.image_size, cfg.num_classes,
                                           d.train_samples or 50 * cfg.batch_size * info.world_size, cfg.seed)
+    mix_options(cfg.data)  # (validated whichever engine runs)
     engine = _pick_engine(cfg, model, train_dataset, dev)
     if not 0.0 <= cfg.ema_decay < 1.0:
         raise ValueError(f"ema_decay must be in [0, 1), got {cfg.ema_decay}")
@@ -432,6 +434,9 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
         _log(f"[train] engine={engine} world={ddist.get_world_size()} steps/epoch={spe} total_steps={total}")
         if has_param_groups(cfg.optim):
             _log_param_groups(runner)
+        if mixes_batches(cfg.data):
+            s = runner.tr.mix_summary() if hasattr(runner.tr, "mix_summary") else mix_options(cfg.data)
+            _log("[train] batch mixing: " + " ".join(f"{k}={v}" for k, v in s.items()))
         if cfg.grad_accum > 1 and cfg.checkpoint_dir and cfg.checkpoint_every and spe % cfg.grad_accum != 0:
             # (one iteration is one micro-batch; a checkpoint carries no accumulator)
             _log(f"[train] warning: steps/epoch={spe} is no multiple of grad_accum={cfg.grad_accum}: a run resumed "
