@@ -127,6 +127,10 @@ class DataConfig:
     erase_mode: str = "const"          # const (0 after normalisation) | pixel (N(0, 1) per pixel and channel)
     erase_scale: Tuple[float, float] = (0.02, 1 / 3)   # rectangle area / image area
     erase_ratio: Tuple[float, float] = (0.3, 3.3)      # rectangle height / width (log-uniform)
+    # TrivialAugmentWide in the native input kernels (torchvision's --auto-augment ta_wide): one of fourteen
+    # uint8-space operations per training image, at one of ta_num_bins strengths. Native engine only.
+    auto_augment: Optional[str] = None  # None | "ta_wide"
+    ta_num_bins: int = 31
 
 
 def mix_options(d: DataConfig) -> Dict[str, Any]:
@@ -142,6 +146,20 @@ def mix_options(d: DataConfig) -> Dict[str, Any]:
 
 def mixes_batches(d: DataConfig) -> bool:
     return d.cutmix_alpha > 0 or d.mixup_alpha > 0 or d.erase_prob > 0
+
+
+def auto_augment_options(d: DataConfig) -> Dict[str, Any]:
+    """The native trainer's ``auto_augment`` / ``ta_num_bins`` from ``cfg.data``, validated (ValueError: an
+    unknown policy name, fewer than two bins)."""
+    from .engine.mix import validate_auto_augment
+    validate_auto_augment(d.auto_augment, d.ta_num_bins)
+    return dict(auto_augment=d.auto_augment, ta_num_bins=d.ta_num_bins)
+
+
+def validate_data(d: DataConfig) -> None:
+    """ValueError for a bad batch-mixing, erasing or auto-augment setting, whichever engine would run."""
+    mix_options(d)
+    auto_augment_options(d)
 
 
 @dataclass

@@ -92,6 +92,12 @@ int dbx_augment_u8(const unsigned char*, bf16*, const float*, const unsigned cha
 int dbx_augment_mix_u8(const unsigned char*, bf16*, const float*, const unsigned char*, int, int, int, int, int, int,
                        float, float, float, float, float, float, const int*, const int*, const float*, const int*, int,
                        unsigned long long, const int*, hipStream_t);
+int dbx_crop_resize_u8(const unsigned char*, unsigned char*, int*, const float*, const unsigned char*, int, int, int,
+                       int, int, hipStream_t);
+int dbx_ta_prepare(const int*, const int*, unsigned char*, int*, int, hipStream_t);
+int dbx_ta_apply_u8(const unsigned char*, bf16*, const int*, const unsigned char*, const int*, int, int, int, float,
+                    float, float, float, float, float, const int*, const int*, const float*, const int*, int,
+                    unsigned long long, const int*, hipStream_t);
 int dbx_small_gemm(int, int, int, int, const dbx::GemmArgs*, hipStream_t);
 long long dbx_mnist_saved_bytes();
 int dbx_mnist_fwd(const float*, const float*, void*, float*, int, unsigned long long, unsigned, int, hipStream_t);
@@ -459,6 +465,28 @@ PYBIND11_MODULE(_C, m) {
                              P<const int*>(perm), P<const int*>(mixbox), P<const float*>(blend), P<const int*>(erase),
                              pixel, seed, P<const int*>(rng_offset), S(st)),
           "augment_mix_u8");
+  });
+  // TrivialAugmentWide (ta_ops.hip): source uint8 -> T (R, G, B, L) + histograms; LUTs and gray means; the
+  // mixing kernel on T
+  m.def("crop_resize_u8", [](uintptr_t in, uintptr_t T, uintptr_t hist, uintptr_t boxes, uintptr_t flip, int N, int Hin,
+                             int Win, int Ho, int Wo, uintptr_t st) {
+    check(dbx_crop_resize_u8(P<const unsigned char*>(in), P<unsigned char*>(T), P<int*>(hist), P<const float*>(boxes),
+                             P<const unsigned char*>(flip), N, Hin, Win, Ho, Wo, S(st)),
+          "crop_resize_u8");
+  });
+  m.def("ta_prepare", [](uintptr_t hist, uintptr_t ops, uintptr_t lut, uintptr_t tmean, int N, uintptr_t st) {
+    check(dbx_ta_prepare(P<const int*>(hist), P<const int*>(ops), P<unsigned char*>(lut), P<int*>(tmean), N, S(st)),
+          "ta_prepare");
+  });
+  m.def("ta_apply_u8", [](uintptr_t T, uintptr_t out, uintptr_t ops, uintptr_t lut, uintptr_t tmean, int N, int Ho,
+                          int Wo, float m0, float m1, float m2, float s0, float s1, float s2, uintptr_t perm,
+                          uintptr_t mixbox, uintptr_t blend, uintptr_t erase, int pixel, unsigned long long seed,
+                          uintptr_t rng_offset, uintptr_t st) {
+    check(dbx_ta_apply_u8(P<const unsigned char*>(T), P<bf16*>(out), P<const int*>(ops), P<const unsigned char*>(lut),
+                          P<const int*>(tmean), N, Ho, Wo, m0, m1, m2, s0, s1, s2, P<const int*>(perm),
+                          P<const int*>(mixbox), P<const float*>(blend), P<const int*>(erase), pixel, seed,
+                          P<const int*>(rng_offset), S(st)),
+          "ta_apply_u8");
   });
   m.def("small_gemm", [](int ta, int tb, int out_f32, int drop, uintptr_t A, uintptr_t B, uintptr_t C, uintptr_t bias_f,
                          uintptr_t bias_h, int M, int N, int K, int lda, int ldb, int ldc, float alpha, int accumulate,

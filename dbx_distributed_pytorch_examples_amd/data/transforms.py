@@ -3,7 +3,8 @@
 CPU-side, torchvision-compatible semantics for the transforms the reference uses
 (`utils/hf_dataset_utilities.py:58-81`, `03_composer/01_cifar_composer_resnet.ipynb:207-215`,
 `02_deepspeed/03_1k_imagenet_deepspeed_resnet.py:43-53`): Compose, Resize, CenterCrop,
-RandomCrop(pad), RandomResizedCrop, RandomHorizontalFlip, Grayscale, ToTensor, Normalize, Lambda.
+RandomCrop(pad), RandomResizedCrop, RandomHorizontalFlip, TrivialAugmentWide, Grayscale, ToTensor, Normalize,
+Lambda.
 Inputs: PIL images or uint8 HWC numpy arrays.
 
 For the native engine the heavy per-sample work moves to the GPU instead: the loader ships
@@ -24,9 +25,9 @@ import numpy as np
 import torch
 
 try:
-    from PIL import Image
+    from PIL import Image, ImageEnhance, ImageOps
 except Exception:  # pragma: no cover
-    Image = None
+    Image = ImageEnhance = ImageOps = None
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -158,6 +159,57 @@ class RandomHorizontalFlip:
             img = _to_pil(img)
             return img.transpose(Image.FLIP_LEFT_RIGHT)
         return img
+
+
+class TrivialAugmentWide:
+    """torchvision's ``TrivialAugmentWide(num_bins=31)`` on PIL images (nearest interpolation, black fill): one of
+    fourteen operations per image, at one of ``num_bins`` strengths, with a random sign where the operation has
+    one. It sits where torchvision puts it: after the crop and the flip, before ``ToTensor``.
+
+    :meth:`apply` takes a row of the table the native engine's kernels take (``engine.mix.ta_row`` /
+    ``sample_trivial_augment``) and performs it with Pillow's own ``ImageEnhance`` / ``ImageOps`` /
+    ``Image.transform``, so it is also the oracle that ``ops/reference.py`` is tested against."""
+
+    def __init__(self, num_bins: int = 31):
+        from ..engine.mix import validate_auto_augment
+        validate_auto_augment("ta_wide", num_bins)
+        self.num_bins = num_bins
+
+    def __call__(self, img):
+        from ..engine.mix import TA_KINDS, ta_magnitude, ta_row
+        img = _to_pil(img)
+        kind, i, sign = random.randrange(TA_KINDS), random.randrange(self.num_bins), random.randrange(2)
+        return self.apply(img, ta_row(kind, ta_magnitude(kind, i, sign, self.num_bins), img.size[1], img.size[0]))
+
+    @staticmethod
+    def apply(img, row):
+        """``row``: int32 [8] = (kind, p, a, b, c, d, e, f), all but the kind fp32 bits."""
+        img = _to_pil(img).convert("RGB")
+        row = np.asarray(row, dtype=np.int32)
+        kind = int(row[0])
+        par = [float(v) for v in row[1:].view(np.float32)]
+        p = par[0]
+        if kind == 0:
+            return img
+        if 1 <= kind <= 5:  # (kind 5's matrix is the one Image.rotate builds: the same pixels)
+            return img.transform(img.size, Image.AFFINE, tuple(par[1:7]), Image.NEAREST, fillcolor=0)
+        if kind == 6:
+            return ImageEnhance.Brightness(img).enhance(p)
+        if kind == 7:
+            return ImageEnhance.Color(img).enhance(p)
+        if kind == 8:
+            return ImageEnhance.Contrast(img).enhance(p)
+        if kind == 9:
+            return ImageEnhance.Sharpness(img).enhance(p)
+        if kind == 10:
+            return ImageOps.posterize(img, int(p))
+        if kind == 11:
+            return ImageOps.solarize(img, p)
+        if kind == 12:
+            return ImageOps.autocontrast(img)
+        if kind == 13:
+            return ImageOps.equalize(img)
+        raise ValueError(f"unknown TrivialAugmentWide kind {kind}")
 
 
 class Grayscale:

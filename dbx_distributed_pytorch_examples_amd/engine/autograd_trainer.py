@@ -224,7 +224,11 @@ class AutogradTrainer:
                  offload_optimizer: bool = False, offload_param: bool = False, bf16: bool = True,
                  stage3: Optional[dict] = None, mixup_alpha: float = 0.0, mix_prob: float = 1.0,
                  mix_switch_prob: float = 0.5, erase_prob: float = 0.0, erase_mode: str = "const",
-                 erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3)):
+                 erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3), auto_augment=None):
+        if auto_augment is not None:  # refused, never ignored
+            raise ValueError(f"auto_augment={auto_augment!r} runs in the native step's input kernels (NativeTrainer); "
+                             f"the autograd engine has no such stage -- put data.transforms.TrivialAugmentWide in the "
+                             f"dataset's transform chain instead")
         from .mix import validate_mix
         validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, erase_mode, erase_scale,
                      erase_ratio)

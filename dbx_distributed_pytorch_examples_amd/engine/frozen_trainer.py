@@ -154,7 +154,11 @@ class FrozenFeatureTrainer:
 
     def __init__(self, model: FrozenBackboneClassifier, batch: int, image_hw: Tuple[int, int], device: torch.device,
                  optim: OptimizerConfig, label_smoothing: float = 0.0, src_hw=None, mean=None, std=None,
-                 bucket_cap_mb: float = 64.0, allreduce_dtype=torch.float32, use_graphs: bool = True):
+                 bucket_cap_mb: float = 64.0, allreduce_dtype=torch.float32, use_graphs: bool = True,
+                 auto_augment=None):
+        if auto_augment is not None:  # refused, never ignored
+            raise ValueError(f"auto_augment={auto_augment!r} needs the native training step (NativeTrainer); the "
+                             f"frozen-backbone trainer runs its backbone in evaluation mode, which never augments")
         self.full_model = model
         self.dev = device
         self.prog = ResNetProgram(_backbone_proxy(model), batch, image_hw, device, src_hw=src_hw, mean=mean, std=std)

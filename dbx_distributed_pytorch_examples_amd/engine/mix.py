@@ -13,7 +13,8 @@ Per step, from one ``numpy.random.Generator``, in this order:
    CutMix: ``lam ~ Beta(a, a)``, a box of area ``1 - lam`` at a uniform centre, clipped, ``lam`` re-derived
    from the clipped area, one permutation (``beta``, ``integers``, ``integers``, ``permutation``: with only
    ``cutmix_alpha`` set this is the whole sequence, the one the trainer has always drawn); blend weight 1;
-4. the erase boxes (:func:`sample_erase_boxes`), drawn only when ``erase_prob > 0``.
+4. the erase boxes (:func:`sample_erase_boxes`), drawn only when ``erase_prob > 0``;
+5. the TrivialAugmentWide table (:func:`sample_trivial_augment`), drawn only with ``auto_augment="ta_wide"``.
 
 MixUp and CutMix are never both applied in one step.
 """
@@ -72,25 +73,130 @@ def sample_erase_boxes(rng: np.random.Generator, n: int, H: int, W: int, prob: f
     return np.where(ok[:, None], box, 0).astype(np.int32)
 
 
+AUTO_AUGMENTS = ("ta_wide",)
+TA_KINDS = 14  # Identity, ShearX, ShearY, TranslateX, TranslateY, Rotate, Brightness, Color, Contrast, Sharpness,
+#                Posterize, Solarize, AutoContrast, Equalize (ops/reference.py, csrc/ta_ops.hip)
+
+
+def validate_auto_augment(auto_augment=None, ta_num_bins=31) -> None:
+    """ValueError for an unknown policy name or fewer than two magnitude bins."""
+    if auto_augment is not None and auto_augment not in AUTO_AUGMENTS:
+        raise ValueError(f"auto_augment must be None or one of {AUTO_AUGMENTS}, got {auto_augment!r}")
+    if not (isinstance(ta_num_bins, int) and not isinstance(ta_num_bins, bool) and ta_num_bins >= 2):
+        raise ValueError(f"ta_num_bins must be an integer >= 2, got {ta_num_bins!r}")
+
+
+def ta_magnitude(kind: int, i: int, sign: int, num_bins: int = 31) -> float:
+    """TrivialAugmentWide's magnitude of bin ``i`` (0 .. num_bins - 1) with ``sign`` (0: +, 1: -, used where
+    the operation is signed): the shear m, the translation t in pixels, the angle in degrees, the enhance
+    factor p, Posterize's bits, Solarize's threshold; 0 for the operations without one."""
+    x = i / (num_bins - 1)
+    sg = -1.0 if sign else 1.0
+    if kind in (1, 2):
+        return sg * 0.99 * x
+    if kind in (3, 4):
+        return sg * int(32.0 * x)
+    if kind == 5:
+        return sg * 135.0 * x
+    if kind in (6, 7, 8, 9):
+        return 1.0 + sg * 0.99 * x
+    if kind == 10:
+        return 8.0 - float(np.rint(i / ((num_bins - 1) / 6)))
+    if kind == 11:
+        return 255.0 - 255.0 * x
+    return 0.0
+
+
+def ta_row(kind: int, mag: float, Ho: int, Wo: int) -> np.ndarray:
+    """One row of the device table, int32 [8] = (kind, p, a, b, c, d, e, f; all but kind fp32 bits), of an
+    operation at magnitude ``mag`` (:func:`ta_magnitude`). Kinds 1-5 carry the inverse affine map of output
+    pixel centres (Pillow's convention); the rotation matrix is Pillow's ``rotate`` about (Wo / 2, Ho / 2),
+    computed in double and stored as fp32."""
+    if not 0 <= kind < TA_KINDS:
+        raise ValueError(f"kind must be in 0..{TA_KINDS - 1}, got {kind}")
+    p, co = 0.0, (1.0, 0.0, 0.0, 0.0, 1.0, 0.0)
+    if kind == 1:
+        co = (1.0, mag, 0.0, 0.0, 1.0, 0.0)
+    elif kind == 2:
+        co = (1.0, 0.0, 0.0, mag, 1.0, 0.0)
+    elif kind == 3:
+        co = (1.0, 0.0, -mag, 0.0, 1.0, 0.0)
+    elif kind == 4:
+        co = (1.0, 0.0, 0.0, 0.0, 1.0, -mag)
+    elif kind == 5:
+        al = -math.radians(mag % 360.0)
+        C, S = round(math.cos(al), 15), round(math.sin(al), 15)
+        cx, cy = Wo / 2.0, Ho / 2.0
+        co = (C, S, (C * -cx + S * -cy) + cx, -S, C, (-S * -cx + C * -cy) + cy)  # (Pillow's order of sums)
+    elif kind in (6, 7, 8, 9, 10, 11):
+        p = mag
+    r = np.zeros(8, dtype=np.int32)
+    r[0] = kind
+    r[1:].view(np.float32)[:] = (p,) + tuple(co)
+    return r
+
+
+def sample_trivial_augment(rng: np.random.Generator, n: int, Ho: int, Wo: int, num_bins: int = 31):
+    """torchvision's TrivialAugmentWide for ``n`` samples: per sample one of the fourteen operations, one of
+    ``num_bins`` magnitudes and a sign, all uniform -- always three vectorised draws (``integers(14, n)``,
+    ``integers(num_bins, n)``, ``integers(2, n)``). Returns ``(kind int32 [n], rows int32 [n, 8])``."""
+    kind = rng.integers(TA_KINDS, size=n)
+    idx = rng.integers(num_bins, size=n)
+    sign = rng.integers(2, size=n)
+    return kind.astype(np.int32), ta_table(kind, idx, sign, Ho, Wo, num_bins)
+
+
+def ta_table(kind, idx, sign, Ho: int, Wo: int, num_bins: int = 31) -> np.ndarray:
+    """The rows of :func:`ta_row` at :func:`ta_magnitude` for arrays of kinds, bins and signs: int32 [n, 8]
+    (vectorised: the trainer builds one per step; only the rotations take a Python loop)."""
+    kind, idx, sign = (np.asarray(v, dtype=np.int64) for v in (kind, idx, sign))
+    n = kind.shape[0]
+    x = idx / (num_bins - 1)
+    sg = np.where(sign != 0, -1.0, 1.0)
+    par = np.zeros((n, 7))
+    par[:, 1] = par[:, 5] = 1.0
+    shear, trans = sg * 0.99 * x, sg * np.trunc(32.0 * x)
+    par[:, 2] = np.where(kind == 1, shear, 0.0)
+    par[:, 4] = np.where(kind == 2, shear, 0.0)
+    par[:, 3] = np.where(kind == 3, -trans, 0.0)
+    par[:, 6] = np.where(kind == 4, -trans, 0.0)
+    p = np.where((kind >= 6) & (kind <= 9), 1.0 + sg * 0.99 * x, 0.0)
+    p = np.where(kind == 10, 8.0 - np.rint(idx / ((num_bins - 1) / 6)), p)
+    par[:, 0] = np.where(kind == 11, 255.0 - 255.0 * x, p)
+    rows = np.zeros((n, 8), dtype=np.int32)
+    rows[:, 0] = kind
+    rows[:, 1:].view(np.float32)[:] = par
+    for j in np.nonzero(kind == 5)[0]:
+        rows[j] = ta_row(5, float(sg[j] * 135.0 * x[j]), Ho, Wo)
+    return rows
+
+
 @dataclass
 class MixDraw:
     """What one step uses: ``kind`` "none" | "mixup" | "cutmix"; ``lam`` the CE weight of the sample's own
     label; ``blend`` the input blend weight (1 unless MixUp); ``perm`` int32 [N]; ``box`` (y0, y1, x0, x1);
-    ``erase`` int32 [N, 4] by source sample, or None when erasing is off."""
+    ``erase`` int32 [N, 4] by source sample, or None when erasing is off; ``ta`` the TrivialAugmentWide
+    table int32 [N, 8] by source sample (:func:`ta_row`), or None when the option is off."""
     kind: str
     lam: float
     blend: float
     perm: np.ndarray
     box: Tuple[int, int, int, int]
     erase: Optional[np.ndarray]
+    ta: Optional[np.ndarray] = None
+
+    def __getitem__(self, name):  # (``last_mix["ta"]``)
+        return getattr(self, name)
 
 
 class MixSampler:
     def __init__(self, rng: np.random.Generator, N: int, H: int, W: int, *, mixup_alpha=0.0, cutmix_alpha=0.0,
                  mix_prob=1.0, mix_switch_prob=0.5, erase_prob=0.0, erase_scale=(0.02, 1 / 3),
-                 erase_ratio=(0.3, 3.3)):
+                 erase_ratio=(0.3, 3.3), auto_augment=None, ta_num_bins=31):
         validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, "const", erase_scale,
                      erase_ratio)
+        validate_auto_augment(auto_augment, ta_num_bins)
+        self.auto_augment, self.ta_num_bins = auto_augment, int(ta_num_bins)
         self.rng, self.N, self.H, self.W = rng, int(N), int(H), int(W)
         self.mixup_alpha, self.cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
         self.mix_prob, self.mix_switch_prob = float(mix_prob), float(mix_switch_prob)
@@ -133,4 +239,7 @@ class MixSampler:
         erase = None
         if self.erase_prob > 0:
             erase = sample_erase_boxes(r, N, H, W, self.erase_prob, self.erase_scale, self.erase_ratio)
-        return MixDraw(kind, lam, blend, perm, box, erase)
+        ta = None
+        if self.auto_augment == "ta_wide":  # (after every earlier draw: the sequences without it are unchanged)
+            ta = sample_trivial_augment(r, N, H, W, self.ta_num_bins)[1]
+        return MixDraw(kind, lam, blend, perm, box, erase, ta)

@@ -37,7 +37,7 @@ from ..parallel.dist import host_sync_for_gloo
 from ..utils import debug as _debug
 from ..utils.profiling import PhaseTimer
 from .hyper import DeviceHyper
-from .mix import MixDraw, MixSampler, validate_mix
+from .mix import MixDraw, MixSampler, validate_auto_augment, validate_mix
 from .program import ResNetProgram, release_dead_graphs
 
 
@@ -81,9 +81,14 @@ class NativeTrainer:
                  engine: Optional[EngineConfig] = None, grad_accum: int = 1, ema_decay: float = 0.0,
                  ema_warmup: bool = False, mixup_alpha: float = 0.0, mix_prob: float = 1.0,
                  mix_switch_prob: float = 0.5, erase_prob: float = 0.0, erase_mode: str = "const",
-                 erase_scale: Tuple[float, float] = (0.02, 1 / 3), erase_ratio: Tuple[float, float] = (0.3, 3.3)):
+                 erase_scale: Tuple[float, float] = (0.02, 1 / 3), erase_ratio: Tuple[float, float] = (0.3, 3.3),
+                 auto_augment: Optional[str] = None, ta_num_bins: int = 31):
         validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, erase_mode, erase_scale,
                      erase_ratio)
+        validate_auto_augment(auto_augment, ta_num_bins)
+        if auto_augment is not None and model.conv1.in_channels != 3:
+            raise ValueError(f"auto_augment={auto_augment!r} needs 3-channel images, the model takes "
+                             f"{model.conv1.in_channels}")
         self.dev = device
         self.cfg = cfg = engine if engine is not None else EngineConfig.current()
         optim = optim or OptimConfig()
@@ -121,18 +126,22 @@ class NativeTrainer:
         # MixUp blends the batch with its permutation instead (weight lam ~ Beta(a, a), the CE's lam too);
         # with both alphas set, each step takes one of the two. Random erasing replaces one rectangle per
         # chosen sample before any mixing. Sampling: engine/mix.py; the kernel: K.augment_u8.
+        # auto_augment="ta_wide" (TrivialAugmentWide): one of fourteen uint8-space operations per sample, drawn
+        # per step into a table that rides in the same arena; the input then runs K.trivial_augment_u8.
         self.cutmix_alpha = float(cutmix_alpha)
         self.mixup_alpha, self.erase_prob, self.erase_mode = float(mixup_alpha), float(erase_prob), erase_mode
         rng_seed = seed + 7919 * (dist.get_rank(process_group) if self.world > 1 else 0)
         self._rng = __import__("numpy").random.default_rng(rng_seed)
         self.last_mix: Optional[MixDraw] = None  # what the last step used
         self._mix, self._mix_ring, self._mix_slot = None, None, 0
-        if self.cutmix_alpha > 0 or self.mixup_alpha > 0 or self.erase_prob > 0:
+        self.auto_augment = auto_augment
+        if self.cutmix_alpha > 0 or self.mixup_alpha > 0 or self.erase_prob > 0 or auto_augment is not None:
             self.prog.enable_mix(blend=self.mixup_alpha > 0, erase=self.erase_prob > 0, erase_mode=erase_mode,
-                                 seed=rng_seed)
+                                 seed=rng_seed, ta=auto_augment is not None)
             self._mix = MixSampler(self._rng, self.prog.N, self.prog.H, self.prog.W, mixup_alpha=mixup_alpha,
                                    cutmix_alpha=cutmix_alpha, mix_prob=mix_prob, mix_switch_prob=mix_switch_prob,
-                                   erase_prob=erase_prob, erase_scale=erase_scale, erase_ratio=erase_ratio)
+                                   erase_prob=erase_prob, erase_scale=erase_scale, erase_ratio=erase_ratio,
+                                   auto_augment=auto_augment, ta_num_bins=ta_num_bins)
         n = self.prog.n_params
         self.mom = torch.zeros(n, device=device)
         self.mom2 = torch.zeros(n, device=device) if optim.name in ("adam", "adamw", "lamb") else None
@@ -683,8 +692,9 @@ class NativeTrainer:
             N = p.N
             if self._mix_ring is None:
                 cuda = self.dev.type == "cuda"
-                self._mix_ring = [(torch.zeros(5 * N + 6, dtype=torch.int32).pin_memory() if cuda
-                                   else torch.zeros(5 * N + 6, dtype=torch.int32),
+                words = p.mix_arena.numel()  # (5 N + 6, and 8 N more with the TrivialAugmentWide table)
+                self._mix_ring = [(torch.zeros(words, dtype=torch.int32).pin_memory() if cuda
+                                   else torch.zeros(words, dtype=torch.int32),
                                    torch.cuda.Event() if cuda else None) for _ in range(4)]
             buf, ev = self._mix_ring[self._mix_slot]
             self._mix_slot = (self._mix_slot + 1) % len(self._mix_ring)
@@ -694,7 +704,9 @@ class NativeTrainer:
             h[:N] = d.perm
             h[N:N + 4] = d.box
             h[N + 4:N + 6].view("float32")[:] = (d.lam, d.blend)
-            h[N + 6:] = d.erase.reshape(-1) if d.erase is not None else 0
+            h[N + 6:5 * N + 6] = d.erase.reshape(-1) if d.erase is not None else 0
+            if d.ta is not None:
+                h[5 * N + 6:] = d.ta.reshape(-1)
             p.mix_arena.copy_(buf, non_blocking=True)
             if ev is not None:
                 ev.record()
@@ -715,7 +727,9 @@ class NativeTrainer:
                 "mix_prob": m.mix_prob if m else 1.0, "mix_switch_prob": m.mix_switch_prob if m else 0.5,
                 "erase_prob": self.erase_prob, "erase_mode": self.erase_mode,
                 "erase_scale": m.erase_scale if m else None, "erase_ratio": m.erase_ratio if m else None,
-                "kernel": "augment_mix_u8" if self.prog.mix_blend is not None else "augment_u8"}
+                "auto_augment": self.auto_augment, "ta_num_bins": m.ta_num_bins if m else 31,
+                "kernel": ("trivial_augment_u8" if self.prog.ta_ops is not None else
+                           "augment_mix_u8" if self.prog.mix_blend is not None else "augment_u8")}
 
     def _set_hyper(self, boundary: bool = True):
         o = self.opt

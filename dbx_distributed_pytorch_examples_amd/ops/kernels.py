@@ -1695,6 +1695,95 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *,
                        _p(offset) if pixel else 0, stream_ptr())
 
 
+ta_work_words = _ref.ta_work_words  # int32 words of trivial_augment_u8's work buffer for (N, Ho, Wo)
+ta_work_views = _ref.ta_work_views  # its (T, hist, lut, mean) views
+
+
+@_dispatch
+def crop_resize_u8(img, T, hist, boxes, flip=None):
+    """uint8 NHWC (3 channels) -> ``T`` uint8 [N, Ho, Wo, 4] = (R, G, B, L): ``augment_u8``'s crop box, bilinear
+    resize and flip rounded to uint8 (``(int)(v + 0.5f)``), L Pillow's gray value of the rounded pixel; ADDS the
+    per-sample histograms of the four channels to ``hist`` int32 [N, 4, 256] (the caller zeroes it)."""
+    N, Hin, Win, Cin = img.shape
+    if Cin != 3:
+        raise ValueError(f"crop_resize_u8 takes 3-channel images, got Cin={Cin}")
+    _, Ho, Wo, C4 = T.shape
+    _chk(img, torch.uint8, "img")
+    _chk(T, torch.uint8, "T", N * Ho * Wo * 4)
+    _chk(hist, torch.int32, "hist", N * 1024)
+    _chk(boxes, torch.float32, "boxes", N * 4)
+    if C4 != 4 or T.data_ptr() % 4:
+        raise ValueError("T: expected [N, Ho, Wo, 4] uint8, 4-byte aligned")
+    if flip is not None:
+        _chk(flip, torch.uint8, "flip", N)
+    C().crop_resize_u8(img.data_ptr(), T.data_ptr(), hist.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Ho, Wo,
+                       stream_ptr())
+
+
+@_dispatch
+def ta_prepare(hist, ops, lut, tmean):
+    """Per sample, from the histograms int32 [N, 4, 256] and the op table int32 [N, 8] (engine/mix.py ``ta_row``):
+    ``lut`` uint8 [N, 3, 256] -- Posterize / Solarize / AutoContrast / Equalize, the identity for every other
+    kind -- and the gray mean ``tmean`` int32 [N] that Contrast blends with."""
+    N = ops.shape[0] if ops.dim() == 2 else -1
+    _ref.check_ta_ops(ops, N)
+    _chk(ops, torch.int32, "ops", N * 8)
+    _chk(hist, torch.int32, "hist", N * 1024)
+    _chk(lut, torch.uint8, "lut", N * 768)
+    _chk(tmean, torch.int32, "tmean", N)
+    C().ta_prepare(hist.data_ptr(), ops.data_ptr(), lut.data_ptr(), tmean.data_ptr(), N, stream_ptr())
+
+
+@_dispatch
+def ta_apply_u8(T, out, ops, lut, tmean, mean, std, *, perm=None, mixbox=None, blend=None, erase=None,
+                erase_mode="const", erase_rng=None):
+    """``T`` uint8 [N, Ho, Wo, 4] -> bf16 NHWC4: per SOURCE sample the TrivialAugmentWide operation of its row of
+    ``ops`` (with ``lut`` / ``tmean`` from :func:`ta_prepare`), then -- exactly as ``augment_u8``'s mixing form --
+    the erase value, the normalisation, the MixUp blend and the CutMix paste. The operation belongs to the
+    source sample, like the erase box: it travels with a pasted or blended sample."""
+    N, Ho, Wo, C4 = T.shape
+    _ref.check_ta_ops(ops, N)
+    _chk(T, torch.uint8, "T")
+    _chk(out, torch.bfloat16, "out", N * Ho * Wo * 4)
+    _chk(ops, torch.int32, "ops", N * 8)
+    _chk(lut, torch.uint8, "lut", N * 768)
+    _chk(tmean, torch.int32, "tmean", N)
+    if C4 != 4 or T.data_ptr() % 4 or lut.data_ptr() % 4:
+        raise ValueError("T: expected [N, Ho, Wo, 4] uint8; T and lut 4-byte aligned")
+    seed, offset = _ref.check_augment_mix(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
+    for t, dt, nm, n in ((perm, torch.int32, "perm", N), (mixbox, torch.int32, "mixbox", 4),
+                         (blend, torch.float32, "blend", 1), (erase, torch.int32, "erase", N * 4)):
+        if t is not None:
+            _chk(t, dt, nm, n)
+    pixel = erase is not None and erase_mode == "pixel"
+    if pixel:
+        _chk(offset, torch.int32, "erase_rng offset", 1)
+    C().ta_apply_u8(T.data_ptr(), out.data_ptr(), ops.data_ptr(), lut.data_ptr(), tmean.data_ptr(), N, Ho, Wo,
+                    float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]), float(std[2]),
+                    _p(perm), _p(mixbox), _p(blend), _p(erase), int(pixel), seed if pixel else 0,
+                    _p(offset) if pixel else 0, stream_ptr())
+
+
+def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None, erase=None,
+                       erase_mode="const", erase_rng=None):
+    """``augment_u8`` with TrivialAugmentWide: ``ops`` int32 [N, 8] is one operation per sample (engine/mix.py
+    ``sample_trivial_augment``), applied to the uint8 image after crop / resize / flip and before the
+    normalisation, erasing and mixing (whose arguments are ``augment_u8``'s). ``work``: an int32 buffer of at
+    least ``ta_work_words(N, Ho, Wo)`` words (T, histograms, LUTs, gray means). Three launches and one
+    memset: :func:`crop_resize_u8`, :func:`ta_prepare`, :func:`ta_apply_u8`. ValueError: ``Cin != 3``, a
+    table that is not [N, 8], a work buffer that is too small."""
+    N, Ho, Wo, _ = out.shape
+    if img.shape[3] != 3:
+        raise ValueError(f"trivial_augment_u8 takes 3-channel images, got Cin={img.shape[3]}")
+    _ref.check_ta_ops(ops, N)
+    T, hist, lut, tmean = _ref.ta_work_views(work, N, Ho, Wo)
+    hist.zero_()
+    crop_resize_u8(img, T, hist, boxes, flip)
+    ta_prepare(hist, ops, lut, tmean)
+    ta_apply_u8(T, out, ops, lut, tmean, mean, std, perm=perm, mixbox=mixbox, blend=blend, erase=erase,
+                erase_mode=erase_mode, erase_rng=erase_rng)
+
+
 def pack_wdesc(descs, device) -> torch.Tensor:
     """Descriptor table of one :func:`weight_prep` launch (csrc/nn_ops.hip WDesc {int64 src, fwd, tr;
     int32 K, RS, C, pad} = 40 bytes per entry) from ``(src, fwd, tr, K, RS, C)`` tuples. ``tr >= 0``: a

@@ -748,31 +748,7 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *,
     if blend is not None or erase is not None:
         # f_s per source sample (erased where erase[s] says so), then the blend, then the paste
         f = _augment_f32(img, out, boxes, mean, std, flip)
-        _, Ho, Wo, _ = out.shape
-        if erase is not None:
-            off = int(offset.reshape(-1)[0]) if offset is not None else 0
-            for s, (y0, y1, x0, x1) in enumerate(erase.reshape(-1, 4).tolist()):
-                y0, y1, x0, x1 = max(y0, 0), min(y1, Ho), max(x0, 0), min(x1, Wo)  # (the kernel tests positions)
-                if y0 >= y1 or x0 >= x1:
-                    continue
-                f[s, y0:y1, x0:x1] = 0.0
-                if erase_mode == "pixel":
-                    oy = torch.arange(y0, y1).view(-1, 1)
-                    ox = torch.arange(x0, x1).view(1, -1)
-                    pix = ((s * Ho + oy) * Wo + ox).reshape(-1).numpy()
-                    f[s, y0:y1, x0:x1, :3] = erase_noise(seed, off, pix).view(y1 - y0, x1 - x0, 3).to(f.device)
-        res = f
-        if perm is not None:
-            fp = f[perm.long()]
-            w = blend.reshape(-1)[0] if blend is not None else None
-            if w is not None and float(w) != 1.0:
-                res = w * f + (1.0 - w) * fp  # fp32 throughout
-            if mixbox is not None:
-                y0, y1, x0, x1 = (int(v) for v in mixbox.tolist())
-                if y0 < y1 and x0 < x1:
-                    res = res.clone()
-                    res[:, y0:y1, x0:x1] = fp[:, y0:y1, x0:x1]
-        out.copy_(res.bfloat16())
+        _mix_tail(f, out, perm, mixbox, blend, erase, erase_mode, seed, offset)
         return
     if perm is not None:  # CutMix: the augmented batch, then the box pasted from sample perm[n]
         augment_u8(img, out, boxes, mean, std, flip)
@@ -784,16 +760,53 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *,
     out.copy_(_augment_f32(img, out, boxes, mean, std, flip).bfloat16())
 
 
+def _mix_tail(f, out, perm, mixbox, blend, erase, erase_mode, seed, offset):
+    """``out`` from the normalised fp32 batch ``f`` by source sample: erase, then the blend, then the paste."""
+    _, Ho, Wo, _ = out.shape
+    if erase is not None:
+        off = int(offset.reshape(-1)[0]) if offset is not None else 0
+        for s, (y0, y1, x0, x1) in enumerate(erase.reshape(-1, 4).tolist()):
+            y0, y1, x0, x1 = max(y0, 0), min(y1, Ho), max(x0, 0), min(x1, Wo)  # (the kernel tests positions)
+            if y0 >= y1 or x0 >= x1:
+                continue
+            f[s, y0:y1, x0:x1] = 0.0
+            if erase_mode == "pixel":
+                oy = torch.arange(y0, y1).view(-1, 1)
+                ox = torch.arange(x0, x1).view(1, -1)
+                pix = ((s * Ho + oy) * Wo + ox).reshape(-1).numpy()
+                f[s, y0:y1, x0:x1, :3] = erase_noise(seed, off, pix).view(y1 - y0, x1 - x0, 3).to(f.device)
+    res = f
+    if perm is not None:
+        fp = f[perm.long()]
+        w = blend.reshape(-1)[0] if blend is not None else None
+        if w is not None and float(w) != 1.0:
+            res = w * f + (1.0 - w) * fp  # fp32 throughout
+        if mixbox is not None:
+            y0, y1, x0, x1 = (int(v) for v in mixbox.tolist())
+            if y0 < y1 and x0 < x1:
+                res = res.clone()
+                res[:, y0:y1, x0:x1] = fp[:, y0:y1, x0:x1]
+    out.copy_(res.bfloat16())
+
+
 def _augment_f32(img, out, boxes, mean, std, flip=None):
     """The normalised fp32 batch [N, Ho, Wo, 4] (pad channel 0) of ``augment_u8`` before its rounding."""
-    N, Hin, Win, Cin = img.shape
     _, Ho, Wo, _ = out.shape
     dev = img.device
-    res = torch.zeros(N, Ho, Wo, 4, device=dev)
-    oy = torch.arange(Ho, device=dev).float()
-    ox = torch.arange(Wo, device=dev).float()
+    res = torch.zeros(img.shape[0], Ho, Wo, 4, device=dev)
     m = torch.tensor(mean, device=dev)
     s = torch.tensor(std, device=dev)
+    for n, v in enumerate(_augment_v255(img, Ho, Wo, boxes, flip)):
+        res[n, ..., :3] = (v / 255.0 - m) / s
+    return res
+
+
+def _augment_v255(img, Ho, Wo, boxes, flip=None):
+    """Per sample, the fp32 bilinear crop-resize [Ho, Wo, 3] in 0..255 (the kernels' expression ``v``)."""
+    N, Hin, Win, Cin = img.shape
+    dev = img.device
+    oy = torch.arange(Ho, device=dev).float()
+    ox = torch.arange(Wo, device=dev).float()
     for n in range(N):
         by, bx, bh, bw = (float(v) for v in boxes[n])
         oxx = (Wo - 1 - ox) if (flip is not None and int(flip[n])) else ox
@@ -806,9 +819,246 @@ def _augment_f32(img, out, boxes, mean, std, flip=None):
         if Cin == 1:
             im = im.expand(Hin, Win, 3)
         im = im[..., :3]
-        v = ((im[y0][:, x0] * (1 - wx) + im[y0][:, x1] * wx) * (1 - wy) + (im[y1][:, x0] * (1 - wx) + im[y1][:, x1] * wx) * wy)
-        res[n, ..., :3] = (v / 255.0 - m) / s
-    return res
+        yield ((im[y0][:, x0] * (1 - wx) + im[y0][:, x1] * wx) * (1 - wy) + (im[y1][:, x0] * (1 - wx) + im[y1][:, x1] * wx) * wy)
+
+
+# ---------------------------------------------------------------------------------------------
+# TrivialAugmentWide (csrc/ta_ops.hip): one of fourteen operations per sample on the uint8 image after
+# crop / resize / flip and before normalisation, erasing and batch mixing. Everything here is integer
+# or fixed-order fp32 (AutoContrast: float64) arithmetic, so the kernels match it bit for bit, and it
+# matches Pillow (the library torchvision calls for these operations) bit for bit except at rotation
+# coordinates within rounding of an integer.
+#
+# Per sample one row of eight 32-bit words (kind int32; p, a, b, c, d, e, f fp32 bits):
+#   0 Identity
+#   1-5 ShearX / ShearY / TranslateX / TranslateY / Rotate: the nearest-neighbour inverse affine map
+#       xi = a (x + .5) + b (y + .5) + c, yi = d (x + .5) + e (y + .5) + f in fp32, every product and sum
+#       rounded on its own, floor, out of the image = 0 (black before normalisation)
+#   6 Brightness blend(0, v, p)   7 Color blend(L, v, p)   8 Contrast blend(mean L, v, p)
+#   9 Sharpness blend(smooth, v, p)   10 Posterize p = bits   11 Solarize p = threshold
+#   12 AutoContrast   13 Equalize
+# ---------------------------------------------------------------------------------------------
+TA_KINDS = 14
+TA_NAMES = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast",
+            "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")
+
+
+def ta_work_words(N: int, Ho: int, Wo: int) -> int:
+    """int32 words of the pipeline's work buffer: T [N, Ho, Wo, 4] uint8 | histograms [N, 4, 256] int32 |
+    lut [N, 3, 256] uint8 | mean [N] int32."""
+    return N * Ho * Wo + N * 1024 + N * 192 + N
+
+
+def ta_work_views(work, N: int, Ho: int, Wo: int):
+    """(T, hist, lut, mean) views of an int32 work buffer of at least :func:`ta_work_words` words."""
+    if work.dtype != torch.int32:
+        raise TypeError(f"work: expected torch.int32, got {work.dtype}")
+    need = ta_work_words(N, Ho, Wo)
+    if work.numel() < need or not work.is_contiguous():
+        raise ValueError(f"work: needs {need} contiguous int32 words for N={N}, {Ho}x{Wo}, got {work.numel()}")
+    w = work.view(-1)
+    a = N * Ho * Wo
+    return (w[:a].view(torch.uint8).view(N, Ho, Wo, 4), w[a:a + N * 1024].view(N, 4, 256),
+            w[a + N * 1024:a + N * 1216].view(torch.uint8).view(N, 3, 256), w[a + N * 1216:a + N * 1217])
+
+
+def check_ta_ops(ops, N: int):
+    if not isinstance(ops, torch.Tensor) or ops.dtype != torch.int32:
+        raise TypeError(f"ops: expected an int32 tensor [N, 8] (kind, p, a..f as fp32 bits), got "
+                        f"{getattr(ops, 'dtype', type(ops))}")
+    if tuple(ops.shape) != (N, 8):
+        raise ValueError(f"ops: expected shape ({N}, 8), got {tuple(ops.shape)}")
+
+
+def _ta_sizes(N: int, **tensors):
+    per = {"hist": 1024, "lut": 768, "tmean": 1}
+    for nm, t in tensors.items():
+        if t.numel() != N * per[nm]:
+            raise ValueError(f"{nm}: expected {N * per[nm]} elements for {N} samples, got {t.numel()}")
+
+
+def ta_luma(rgb):
+    """Pillow's L of a numpy integer [..., 3] array."""
+    import numpy as np
+    a = np.asarray(rgb).astype(np.int64)
+    return (a[..., 0] * 19595 + a[..., 1] * 38470 + a[..., 2] * 7471 + 0x8000) >> 16
+
+
+def ta_pack(rgb) -> torch.Tensor:
+    """uint8 [..., 3] -> the pipeline's image T, uint8 [..., 4] = (R, G, B, L)."""
+    import numpy as np
+    a = rgb.cpu().numpy() if isinstance(rgb, torch.Tensor) else np.asarray(rgb)
+    return torch.from_numpy(np.concatenate([a, ta_luma(a)[..., None].astype(np.uint8)], -1).astype(np.uint8))
+
+
+def ta_histograms(T) -> torch.Tensor:
+    """int32 [N, 4, 256] of T uint8 [N, Ho, Wo, 4]."""
+    import numpy as np
+    a = T.cpu().numpy()
+    return torch.from_numpy(np.stack([np.stack([np.bincount(a[n, ..., c].ravel(), minlength=256) for c in range(4)])
+                                      for n in range(a.shape[0])]).astype(np.int32))
+
+
+def _ta_blend(d, v, p):
+    """``t = d + p (v - d)`` in fp32 (product and sum rounded separately); truncation inside [0, 1], else
+    clamped to 0..255 first (Pillow's ``Image.blend``)."""
+    import numpy as np
+    p = np.float32(p)
+    d, v = d.astype(np.float32), v.astype(np.float32)
+    t = d + p * (v - d)
+    if 0.0 <= p <= 1.0:
+        return t.astype(np.int64).astype(np.uint8)
+    return np.where(t <= 0, 0, np.where(t >= 255, 255, t.astype(np.int64))).astype(np.uint8)
+
+
+def _ta_smooth(a):
+    import numpy as np
+    h, w, _ = a.shape
+    o = a.copy()
+    if h < 3 or w < 3:
+        return o
+    A = a.astype(np.int64)
+    S = np.zeros((h - 2, w - 2, 3), np.int64)
+    for dy in range(3):
+        for dx in range(3):
+            S += A[dy:dy + h - 2, dx:dx + w - 2] * (5 if dy == 1 and dx == 1 else 1)
+    o[1:-1, 1:-1] = (S + 6) // 13
+    return o
+
+
+def _ta_affine(a, co):
+    import numpy as np
+    h, w, _ = a.shape
+    f = np.float32
+    yy, xx = np.mgrid[0:h, 0:w]
+    xs, ys = xx.astype(f) + f(.5), yy.astype(f) + f(.5)
+    co = [f(v) for v in co]
+    xi = (co[0] * xs + co[1] * ys) + co[2]
+    yi = (co[3] * xs + co[4] * ys) + co[5]
+    xf, yf = np.floor(xi).astype(np.int64), np.floor(yi).astype(np.int64)
+    ok = (xf >= 0) & (xf < w) & (yf >= 0) & (yf < h)
+    o = np.zeros_like(a)
+    o[ok] = a[yf[ok], xf[ok]]
+    return o
+
+
+def ta_lut_mean(hist, row):
+    """(lut uint8 [3, 256], mean int) of one sample from its histograms int [4, 256] and its op row (numpy
+    int32 [8]): ``lut`` is the identity unless the kind is 10-13; ``mean = (2 sum L + n) // (2 n)``."""
+    import numpy as np
+    hist = np.asarray(hist).astype(np.int64)
+    kind = min(max(int(row[0]), 0), TA_KINDS - 1)
+    p = float(np.asarray(row[1:2]).view(np.float32)[0])
+    x = np.arange(256, dtype=np.int64)
+    lut = np.tile(x, (3, 1))
+    if kind == 10:
+        bits = min(max(int(p), 0), 8)
+        lut[:] = x & ((0xFF << (8 - bits)) & 0xFF)
+    elif kind == 11:
+        lut[:] = np.where(x.astype(np.float32) < np.float32(p), x, 255 - x)
+    elif kind in (12, 13):
+        for c in range(3):
+            nz = np.nonzero(hist[c])[0]
+            if len(nz) < 2:
+                continue
+            lo, hi = int(nz[0]), int(nz[-1])
+            if kind == 12:
+                scale = 255.0 / (hi - lo)
+                off = -lo * scale
+                lut[c] = [min(255, max(0, int(i * scale + off))) for i in range(256)]
+            else:
+                step = (int(hist[c].sum()) - int(hist[c][hi])) // 255
+                if step == 0:
+                    continue
+                n = step // 2
+                for i in range(256):
+                    lut[c, i] = min(255, n // step)
+                    n += int(hist[c][i])
+    n = int(hist[3].sum())
+    mean = (2 * int((hist[3] * x).sum()) + n) // (2 * n) if n else 0
+    return lut.astype(np.uint8), mean
+
+
+def ta_apply_image(a, row, lut=None, mean=None):
+    """One sample: numpy uint8 [H, W, 3] and its op row (numpy int32 [8]) -> the augmented uint8 [H, W, 3].
+    ``lut`` / ``mean`` default to those of the image itself."""
+    import numpy as np
+    a = np.ascontiguousarray(a[..., :3])
+    row = np.asarray(row, dtype=np.int32)
+    kind = min(max(int(row[0]), 0), TA_KINDS - 1)
+    par = row[1:].view(np.float32)
+    if lut is None or mean is None:
+        T = ta_pack(a[None])
+        lut, mean = ta_lut_mean(ta_histograms(T)[0].numpy(), row)
+    if kind == 0:
+        return a.copy()
+    if kind <= 5:
+        return _ta_affine(a, par[1:7])
+    if kind == 6:
+        return _ta_blend(np.zeros_like(a), a, par[0])
+    if kind == 7:
+        return _ta_blend(np.repeat(ta_luma(a)[..., None], 3, -1), a, par[0])
+    if kind == 8:
+        return _ta_blend(np.full_like(a, mean), a, par[0])
+    if kind == 9:
+        return _ta_blend(_ta_smooth(a), a, par[0])
+    return np.stack([np.asarray(lut)[c][a[..., c]] for c in range(3)], -1).astype(np.uint8)
+
+
+def crop_resize_u8(img, T, hist, boxes, flip=None):
+    """T uint8 [N, Ho, Wo, 4] = (R, G, B, L) of ``u8 = (int)(v + 0.5f)`` with v the fp32 bilinear expression of
+    ``augment_u8``; adds the per-sample histograms to ``hist`` int32 [N, 4, 256]."""
+    N, Ho, Wo, _ = T.shape
+    if img.shape[3] != 3:
+        raise ValueError(f"crop_resize_u8 takes 3-channel images, got Cin={img.shape[3]}")
+    for n, v in enumerate(_augment_v255(img, Ho, Wo, boxes, flip)):
+        u = (v + 0.5).to(torch.int64).clamp(0, 255).to(torch.uint8)
+        T[n].copy_(ta_pack(u))
+    hist.add_(ta_histograms(T).view(hist.shape))
+
+
+def ta_prepare(hist, ops, lut, tmean):
+    """Per sample ``lut`` uint8 [N, 3, 256] and ``tmean`` int32 [N] from the histograms and the op table."""
+    N = ops.shape[0] if ops.dim() == 2 else -1
+    check_ta_ops(ops, N)
+    _ta_sizes(N, hist=hist, lut=lut, tmean=tmean)
+    h, o = hist.view(N, 4, 256).numpy(), ops.numpy()
+    for n in range(N):
+        l, m = ta_lut_mean(h[n], o[n])
+        lut.view(N, 3, 256)[n].copy_(torch.from_numpy(l))
+        tmean.view(-1)[n] = m
+
+
+def ta_apply_u8(T, out, ops, lut, tmean, mean, std, *, perm=None, mixbox=None, blend=None, erase=None,
+                erase_mode="const", erase_rng=None):
+    """The mixing kernel on T: per source sample the operation of ``ops``, the erase value, the
+    normalisation; then the blend and the paste as in ``augment_u8``."""
+    N, Ho, Wo, _ = T.shape
+    check_ta_ops(ops, N)
+    _ta_sizes(N, lut=lut, tmean=tmean)
+    seed, offset = check_augment_mix(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
+    a, o = T.numpy(), ops.numpy()
+    l, mn = lut.view(N, 3, 256).numpy(), tmean.view(-1).tolist()
+    f = torch.zeros(N, Ho, Wo, 4)
+    m, s = torch.tensor(mean), torch.tensor(std)
+    for n in range(N):
+        v = torch.from_numpy(ta_apply_image(a[n], o[n], l[n], mn[n])).float()
+        f[n, ..., :3] = (v / 255.0 - m) / s
+    _mix_tail(f, out, perm, mixbox, blend, erase, erase_mode, seed, offset)
+
+
+def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None,
+                       erase=None, erase_mode="const", erase_rng=None):
+    N, Ho, Wo, _ = out.shape
+    if img.shape[3] != 3:
+        raise ValueError(f"trivial_augment_u8 takes 3-channel images, got Cin={img.shape[3]}")
+    check_ta_ops(ops, N)
+    T, hist, lut, tmean = ta_work_views(work, N, Ho, Wo)
+    hist.zero_()
+    crop_resize_u8(img, T, hist, boxes, flip)
+    ta_prepare(hist, ops, lut, tmean)
+    ta_apply_u8(T, out, ops, lut, tmean, mean, std, perm=perm, mixbox=mixbox, blend=blend, erase=erase,
+                erase_mode=erase_mode, erase_rng=erase_rng)
 
 
 def weight_prep(master, wbuf, desc_dev, nlayers):

@@ -35,8 +35,8 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from ..config import (TrainConfig, from_deepspeed, has_param_groups, mix_options, mixes_batches, parse_duration,
-                      to_dict)
+from ..config import (TrainConfig, auto_augment_options, from_deepspeed, has_param_groups, mix_options,
+                      mixes_batches, parse_duration, to_dict, validate_data)
 from ..models import build_model
 from ..parallel import dist as ddist
 from ..parallel.sampler import ShardSampler
@@ -148,7 +148,8 @@ class _Native:
                                     bucket_cap_mb=cfg.bucket_cap_mb, allreduce_dtype=ar,
                                     src_hw=(h, w), mean=mean, std=std, zero_stage=cfg.zero.stage,
                                     seed=cfg.seed, grad_accum=cfg.grad_accum, ema_decay=cfg.ema_decay,
-                                    ema_warmup=cfg.ema_warmup, **mix_options(cfg.data))
+                                    ema_warmup=cfg.ema_warmup, **mix_options(cfg.data),
+                                    **auto_augment_options(cfg.data))
         self.ema_eval = bool(cfg.ema_eval)
         self.eval_topk, self.eval_graph = _eval_topk(cfg), bool(cfg.eval_graph)
         if not cfg.data.augment:
@@ -380,8 +381,19 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
         else:
             train_dataset = build_dataset(d.dataset, d.root, True, None, d.image_size, cfg.num_classes,
                                           d.train_samples or 50 * cfg.batch_size * info.world_size, cfg.seed)
-    mix_options(cfg.data)  # (validated whichever engine runs)
+    validate_data(cfg.data)  # (validated whichever engine runs)
     engine = _pick_engine(cfg, model, train_dataset, dev)
+    if cfg.data.auto_augment is not None:  # refused, never ignored
+        from ..models.wrappers import FrozenBackboneClassifier
+        if engine != "native" or isinstance(model, FrozenBackboneClassifier):
+            raise ValueError(f"data.auto_augment={cfg.data.auto_augment!r} needs the native training step "
+                             f"(NativeTrainer, whose input kernels apply it); this run would use the "
+                             f"{'frozen-backbone' if engine == 'native' else engine} engine, which has no such "
+                             f"input stage")
+        in_ch = getattr(getattr(model, "conv1", None), "in_channels", 3)
+        if in_ch != 3:
+            raise ValueError(f"data.auto_augment={cfg.data.auto_augment!r} needs 3-channel images, the model "
+                             f"takes {in_ch}")
     if not 0.0 <= cfg.ema_decay < 1.0:
         raise ValueError(f"ema_decay must be in [0, 1), got {cfg.ema_decay}")
     if cfg.ema_decay > 0:
@@ -434,7 +446,7 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
         _log(f"[train] engine={engine} world={ddist.get_world_size()} steps/epoch={spe} total_steps={total}")
         if has_param_groups(cfg.optim):
             _log_param_groups(runner)
-        if mixes_batches(cfg.data):
+        if mixes_batches(cfg.data) or cfg.data.auto_augment is not None:
             s = runner.tr.mix_summary() if hasattr(runner.tr, "mix_summary") else mix_options(cfg.data)
             _log("[train] batch mixing: " + " ".join(f"{k}={v}" for k, v in s.items()))
         if cfg.grad_accum > 1 and cfg.checkpoint_dir and cfg.checkpoint_every and spe % cfg.grad_accum != 0:
