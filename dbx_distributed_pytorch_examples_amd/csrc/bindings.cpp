@@ -459,14 +459,14 @@ PYBIND11_MODULE(_C, m) {
                              int Cin, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1, float s2,
                              uintptr_t perm, uintptr_t mixbox, uintptr_t blend, uintptr_t erase, int pixel,
                              unsigned long long seed, uintptr_t rng_offset, uintptr_t st) {
-    // the augment kernel with a MixUp blend and / or random erasing (nn_ops.hip augment_mix_u8_kernel)
+    // the augment kernel with a MixUp blend and / or random erasing (input_ops.hip augment_mix_u8_kernel)
     check(dbx_augment_mix_u8(P<const unsigned char*>(in), P<bf16*>(out), P<const float*>(boxes),
                              P<const unsigned char*>(flip), N, Hin, Win, Cin, Ho, Wo, m0, m1, m2, s0, s1, s2,
                              P<const int*>(perm), P<const int*>(mixbox), P<const float*>(blend), P<const int*>(erase),
                              pixel, seed, P<const int*>(rng_offset), S(st)),
           "augment_mix_u8");
   });
-  // TrivialAugmentWide (ta_ops.hip): source uint8 -> T (R, G, B, L) + histograms; LUTs and gray means; the
+  // TrivialAugmentWide (input_ops.hip): source uint8 -> T (R, G, B, L) + histograms; LUTs and gray means; the
   // mixing kernel on T
   m.def("crop_resize_u8", [](uintptr_t in, uintptr_t T, uintptr_t hist, uintptr_t boxes, uintptr_t flip, int N, int Hin,
                              int Win, int Ho, int Wo, uintptr_t st) {

@@ -1,7 +1,7 @@
 // Memory-bound CNN ops for the NHWC bf16 ResNet programs (gfx950).
 //
 // The reference executes these as separate MIOpen/ATen passes (BatchNorm fwd/bwd, ReLU,
-// residual add, maxpool, softmax-CE, foreach optimizer: SURVEY.md §2.4 K6-K17, K20). Here each
+// residual add, maxpool, softmax-CE, foreach optimizer: SURVEY.md §2.4 K6-K17). Here each
 // op is one vectorised (16 B/lane) pass, and the passes are fused where the ResNet dataflow
 // allows it:
 //   * BN statistics come from the conv epilogue (conv_igemm.hip); bn_finalize turns the sharded
@@ -17,7 +17,6 @@
 //   * SGD-momentum / Adam(W) over the flat fp32 master buffer, writing the bf16 compute copy.
 #include "common.h"
 #include "bn_fin.h"
-#include "philox.h"
 
 namespace dbx {
 
@@ -1232,244 +1231,6 @@ __global__ void clip_factor_kernel(const double* sumsq, float max_norm, float* o
 }
 
 // ----------------------------------------------------------------------------------------
-// Input: uint8 NHWC [N][H][W][3] -> bf16 NHWC4 normalised ((x/255 - mean)/std, ch3 = 0),
-// optional per-sample horizontal flip (flags[n] != 0).
-// ----------------------------------------------------------------------------------------
-__global__ void normalize_u8_kernel(const unsigned char* __restrict__ in, bf16* __restrict__ out,
-                                    const unsigned char* __restrict__ flip, int N, int H, int W, int Cin,
-                                    float m0, float m1, float m2, float s0, float s1, float s2) {
-  const long long total = (long long)N * H * W;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-    const int w = (int)(i % W);
-    const long long nh = i / W;
-    const int n = (int)(nh / H);
-    const int ws = (flip && flip[n]) ? (W - 1 - w) : w;
-    const unsigned char* src = in + ((nh * W) + ws) * Cin;
-    float f0, f1, f2;
-    if (Cin == 1) { f0 = f1 = f2 = src[0] * (1.f / 255.f); }
-    else { f0 = src[0] * (1.f / 255.f); f1 = src[1] * (1.f / 255.f); f2 = src[2] * (1.f / 255.f); }
-    bf16x4 o = {(bf16)((f0 - m0) / s0), (bf16)((f1 - m1) / s1), (bf16)((f2 - m2) / s2), (bf16)0.f};
-    *reinterpret_cast<bf16x4*>(out + i * 4) = o;
-  }
-}
-
-// ----------------------------------------------------------------------------------------
-// GPU input augmentation: uint8 NHWC [N][Hin][Win][Cin] -> bf16 NHWC4
-// [N][Ho][Wo][4]: per-sample crop box (y0, x0, h, w in source pixels, float) resized to Ho x Wo
-// with bilinear sampling (pixel-centre convention, edge clamp), optional horizontal flip,
-// (x/255 - mean)/std, channel 3 = 0. Covers RandomResizedCrop / RandomCrop(pad) / Resize /
-// CenterCrop + RandomHorizontalFlip + Normalize of the reference's CPU transform chains.
-// ----------------------------------------------------------------------------------------
-// One block per output row (n, oy): the box, flip and the two source rows are block-uniform, so
-// per pixel only the column interpolation is computed (32-bit index math throughout).
-// CutMix (Composer's CutMix(alpha=1), `03_composer/01_cifar_composer_resnet.ipynb:430`):
-// with perm / mixbox set, output pixels inside the batch-wide box [y0, y1) x [x0, x1) come from
-// sample perm[n] -- sampled with ITS crop box and flip, i.e. exactly the pixels of the augmented
-// image perm[n] at the same output position (Composer pastes after the per-sample transforms).
-__global__ __launch_bounds__(256) void augment_u8_kernel(const unsigned char* __restrict__ in, bf16* __restrict__ out,
-                                                         const float* __restrict__ boxes,
-                                                         const unsigned char* __restrict__ flip, int N, int Hin,
-                                                         int Win, int Cin, int Ho, int Wo, float m0, float m1,
-                                                         float m2, float s0, float s1, float s2,
-                                                         const int* __restrict__ perm, const int* __restrict__ mixbox) {
-  constexpr int kRowMax = 4096;
-  __shared__ __attribute__((aligned(16))) unsigned char srow[2][kRowMax];
-  const int my0 = mixbox ? mixbox[0] : 0, my1 = mixbox ? mixbox[1] : 0;
-  const int mx0 = mixbox ? mixbox[2] : 0, mx1 = mixbox ? mixbox[3] : 0;
-  const float i0 = 1.f / (255.f * s0), i1 = 1.f / (255.f * s1), i2 = 1.f / (255.f * s2);
-  for (int row = blockIdx.x; row < N * Ho; row += gridDim.x) {  // row = n * Ho + oy
-  const int n = row / Ho, oy = row - n * Ho;
-  const bool mixrow = perm && oy >= my0 && oy < my1 && mx0 < mx1;  // block-uniform
-  // pass 0: sample n outside the box (everywhere when not mixing); pass 1: sample perm[n] inside
-  for (int pass = 0; pass < (mixrow ? 2 : 1); ++pass) {
-  const int sn = pass ? perm[n] : n;
-  const int xlo = pass ? mx0 : 0, xhi = pass ? mx1 : Wo;
-  const float by = boxes[4 * sn], bx = boxes[4 * sn + 1], bh = boxes[4 * sn + 2], bw = boxes[4 * sn + 3];
-  const bool fl = flip && flip[sn];
-  float sy = by + (oy + 0.5f) * bh / Ho - 0.5f;
-  sy = fminf(fmaxf(sy, 0.f), (float)(Hin - 1));
-  const int y0 = (int)sy, y1 = min(y0 + 1, Hin - 1);
-  const float wy = sy - y0;
-  const unsigned char* g0 = in + ((size_t)sn * Hin + y0) * Win * Cin;
-  const unsigned char* g1 = in + ((size_t)sn * Hin + y1) * Win * Cin;
-  // the two source rows are staged in LDS with 16-byte loads (the bilinear taps are byte gathers)
-  const int rb = Win * Cin;
-  const bool staged = rb <= kRowMax && (((size_t)g0 | (size_t)g1) & 15) == 0 && (rb & 15) == 0;  // block-uniform
-  if (staged) {
-    for (int o = threadIdx.x * 16; o < rb; o += blockDim.x * 16) {
-      *reinterpret_cast<u32x4*>(&srow[0][o]) = *reinterpret_cast<const u32x4*>(g0 + o);
-      *reinterpret_cast<u32x4*>(&srow[1][o]) = *reinterpret_cast<const u32x4*>(g1 + o);
-    }
-    __syncthreads();
-  }
-  const float sxs = bw / Wo;
-  auto body = [&](const unsigned char* r0, const unsigned char* r1) __attribute__((always_inline)) {
-    for (int ox = xlo + threadIdx.x; ox < xhi; ox += blockDim.x) {
-      if (mixrow && !pass && ox >= mx0 && ox < mx1) continue;  // pasted by pass 1
-      const int oxx = fl ? (Wo - 1 - ox) : ox;
-      float sx = bx + (oxx + 0.5f) * sxs - 0.5f;
-      sx = fminf(fmaxf(sx, 0.f), (float)(Win - 1));
-      const int x0 = (int)sx, x1 = min(x0 + 1, Win - 1);
-      const float wx = sx - x0;
-      float v[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int cc = Cin == 1 ? 0 : c;
-        const float a = r0[x0 * Cin + cc], b = r0[x1 * Cin + cc];
-        const float d = r1[x0 * Cin + cc], e = r1[x1 * Cin + cc];
-        v[c] = (a * (1.f - wx) + b * wx) * (1.f - wy) + (d * (1.f - wx) + e * wx) * wy;  // 0..255
-      }
-      bf16x4 o = {(bf16)(v[0] * i0 - m0 / s0), (bf16)(v[1] * i1 - m1 / s1), (bf16)(v[2] * i2 - m2 / s2), (bf16)0.f};
-      *reinterpret_cast<bf16x4*>(out + ((size_t)row * Wo + ox) * 4) = o;
-    }
-  };
-  if (staged) body(&srow[0][0], &srow[1][0]);  // LDS byte gathers (ds_read_u8)
-  else body(g0, g1);
-  __syncthreads();  // srow reuse by the next pass / row
-  }
-  }
-}
-
-// The mixing form of the augment kernel (MixUp blend, random erasing; the CutMix paste as above).
-// With f_s(oy, ox) the normalised fp32 pixel of source sample s -- the plain kernel's expression, or
-// the erase value where (oy, ox) lies in erase[s] = (y0, y1, x0, x1), output coordinates --
-//   out[n] = f_perm[n]                              inside mixbox
-//          = bf16(w f_n + (1 - w) f_perm[n])        elsewhere, w = blend[0] read from memory
-// Erasing belongs to the source sample (torchvision / timm erase before they mix), so an erased
-// rectangle travels with a pasted or blended sample. w == 1 never reads the second sample (block-
-// uniform) and then, like an all-empty erase table, gives the plain kernel's bits. Erase value: 0
-// (pixel == 0), or one N(0, 1) draw per pixel and channel from the Philox counter
-// pix = (s Ho + oy) Wo + ox (Box-Muller on its four words, precise logf / sqrtf / cospif / sinpif):
-// a function of (seed, offset, source sample, position), so a copy of a sample carries its noise.
-// A row stages the two source rows of both samples (4 x 4096 B of LDS) when all four can be.
-struct AugMix {
-  const float* blend;         // fp32[1]; null: 1
-  const int* erase;           // int32 [N][4]; null: none
-  const int* rng_offset;      // int32[1] (pixel mode)
-  unsigned long long seed;
-  int pixel;
-};
-struct AugRow {  // what is uniform over one output row of one source sample
-  const unsigned char *g0, *g1;
-  float bx, sxs, wy;
-  int sn, ey0, ey1, ex0, ex1;
-  bool fl;
-};
-__device__ __forceinline__ AugRow aug_row(const unsigned char* __restrict__ in, const float* __restrict__ boxes,
-                                          const unsigned char* __restrict__ flip, const int* __restrict__ erase,
-                                          int sn, int oy, int Hin, int Win, int Cin, int Ho, int Wo) {
-  AugRow r;
-  const float by = boxes[4 * sn], bh = boxes[4 * sn + 2], bw = boxes[4 * sn + 3];
-  r.bx = boxes[4 * sn + 1];
-  r.fl = flip && flip[sn];
-  float sy = by + (oy + 0.5f) * bh / Ho - 0.5f;
-  sy = fminf(fmaxf(sy, 0.f), (float)(Hin - 1));
-  const int y0 = (int)sy, y1 = min(y0 + 1, Hin - 1);
-  r.wy = sy - y0;
-  r.g0 = in + ((size_t)sn * Hin + y0) * Win * Cin;
-  r.g1 = in + ((size_t)sn * Hin + y1) * Win * Cin;
-  r.sxs = bw / Wo;
-  r.sn = sn;
-  r.ey0 = r.ey1 = r.ex0 = r.ex1 = 0;
-  if (erase && oy >= erase[4 * sn] && oy < erase[4 * sn + 1]) {  // (an empty box erases no column either)
-    r.ey0 = erase[4 * sn]; r.ey1 = erase[4 * sn + 1]; r.ex0 = erase[4 * sn + 2]; r.ex1 = erase[4 * sn + 3];
-  }
-  return r;
-}
-
-__global__ __launch_bounds__(256) void augment_mix_u8_kernel(const unsigned char* __restrict__ in, bf16* __restrict__ out,
-                                                             const float* __restrict__ boxes,
-                                                             const unsigned char* __restrict__ flip, int N, int Hin,
-                                                             int Win, int Cin, int Ho, int Wo, float m0, float m1,
-                                                             float m2, float s0, float s1, float s2,
-                                                             const int* __restrict__ perm,
-                                                             const int* __restrict__ mixbox, const AugMix am) {
-  constexpr int kRowMax = 4096;
-  __shared__ __attribute__((aligned(16))) unsigned char srow[4][kRowMax];
-  const int my0 = mixbox ? mixbox[0] : 0, my1 = mixbox ? mixbox[1] : 0;
-  const int mx0 = mixbox ? mixbox[2] : 0, mx1 = mixbox ? mixbox[3] : 0;
-  const float i0 = 1.f / (255.f * s0), i1 = 1.f / (255.f * s1), i2 = 1.f / (255.f * s2);
-  const float w = (am.blend && perm) ? am.blend[0] : 1.f;
-  const bool blendrow = w != 1.f;  // grid-uniform
-  const unsigned roff = am.pixel ? (unsigned)am.rng_offset[0] : 0u;
-  for (int row = blockIdx.x; row < N * Ho; row += gridDim.x) {  // row = n * Ho + oy
-    const int n = row / Ho, oy = row - n * Ho;
-    const bool mixrow = perm && oy >= my0 && oy < my1 && mx0 < mx1;  // block-uniform
-    const bool two = mixrow || blendrow;                              // the row reads sample perm[n]
-    const AugRow A = aug_row(in, boxes, flip, am.erase, n, oy, Hin, Win, Cin, Ho, Wo);
-    const AugRow P = two ? aug_row(in, boxes, flip, am.erase, min(max(perm[n], 0), N - 1), oy, Hin, Win, Cin, Ho, Wo) : A;
-    const int rb = Win * Cin;
-    const bool staged = rb <= kRowMax && (rb & 15) == 0 &&
-                        (((size_t)A.g0 | (size_t)A.g1 | (size_t)P.g0 | (size_t)P.g1) & 15) == 0;  // block-uniform
-    if (staged) {
-      for (int o = threadIdx.x * 16; o < rb; o += blockDim.x * 16) {
-        *reinterpret_cast<u32x4*>(&srow[0][o]) = *reinterpret_cast<const u32x4*>(A.g0 + o);
-        *reinterpret_cast<u32x4*>(&srow[1][o]) = *reinterpret_cast<const u32x4*>(A.g1 + o);
-        if (two) {
-          *reinterpret_cast<u32x4*>(&srow[2][o]) = *reinterpret_cast<const u32x4*>(P.g0 + o);
-          *reinterpret_cast<u32x4*>(&srow[3][o]) = *reinterpret_cast<const u32x4*>(P.g1 + o);
-        }
-      }
-      __syncthreads();
-    }
-    // f_s at column ox: the erase value inside the sample's erase box, else the plain kernel's pixel
-    auto px = [&](const AugRow& r, const unsigned char* r0, const unsigned char* r1, int ox, float (&f)[3])
-                  __attribute__((always_inline)) {
-      if (ox >= r.ex0 && ox < r.ex1) {  // (the row test is in aug_row)
-        f[0] = f[1] = f[2] = 0.f;
-        if (am.pixel) {
-          unsigned u[4];
-          philox4x32_10(((unsigned long long)r.sn * Ho + oy) * Wo + ox, am.seed, roff, u);
-          const float k24 = 1.f / 16777216.f;
-          const float r01 = sqrtf(-2.f * logf((float)((u[0] >> 8) + 1u) * k24));
-          const float a01 = 2.f * ((float)(u[1] >> 8) * k24);
-          f[0] = r01 * cospif(a01);
-          f[1] = r01 * sinpif(a01);
-          f[2] = sqrtf(-2.f * logf((float)((u[2] >> 8) + 1u) * k24)) * cospif(2.f * ((float)(u[3] >> 8) * k24));
-        }
-        return;
-      }
-      const int oxx = r.fl ? (Wo - 1 - ox) : ox;
-      float sx = r.bx + (oxx + 0.5f) * r.sxs - 0.5f;
-      sx = fminf(fmaxf(sx, 0.f), (float)(Win - 1));
-      const int x0 = (int)sx, x1 = min(x0 + 1, Win - 1);
-      const float wx = sx - x0, wy = r.wy;
-      float v[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int cc = Cin == 1 ? 0 : c;
-        const float a = r0[x0 * Cin + cc], b = r0[x1 * Cin + cc];
-        const float d = r1[x0 * Cin + cc], e = r1[x1 * Cin + cc];
-        v[c] = (a * (1.f - wx) + b * wx) * (1.f - wy) + (d * (1.f - wx) + e * wx) * wy;  // 0..255
-      }
-      f[0] = v[0] * i0 - m0 / s0; f[1] = v[1] * i1 - m1 / s1; f[2] = v[2] * i2 - m2 / s2;
-    };
-    auto body = [&](const unsigned char* a0, const unsigned char* a1, const unsigned char* p0, const unsigned char* p1)
-                    __attribute__((always_inline)) {
-      for (int ox = threadIdx.x; ox < Wo; ox += blockDim.x) {
-        float f[3];
-        if (mixrow && ox >= mx0 && ox < mx1) {
-          px(P, p0, p1, ox, f);
-        } else {
-          px(A, a0, a1, ox, f);
-          if (blendrow) {
-            float q[3];
-            px(P, p0, p1, ox, q);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) f[c] = w * f[c] + (1.f - w) * q[c];
-          }
-        }
-        bf16x4 o = {(bf16)f[0], (bf16)f[1], (bf16)f[2], (bf16)0.f};
-        *reinterpret_cast<bf16x4*>(out + ((size_t)row * Wo + ox) * 4) = o;
-      }
-    };
-    if (staged) body(&srow[0][0], &srow[1][0], &srow[2][0], &srow[3][0]);  // LDS byte gathers
-    else body(A.g0, A.g1, P.g0, P.g1);
-    __syncthreads();  // srow reuse by the next row
-  }
-}
-
-// ----------------------------------------------------------------------------------------
 // Weight prep: fp32 KRSC master -> bf16 KRSC (fwd) and bf16 CRSK (dgrad) ; batched over layers
 // ----------------------------------------------------------------------------------------
 struct WDesc { long long src, fwd, tr; int K, RS, C, pad; };
@@ -1885,29 +1646,6 @@ extern "C" int dbx_sumsq(const float* x, long long n, double* out, hipStream_t s
 }
 extern "C" int dbx_clip_factor(const double* sumsq, float max_norm, float* out, hipStream_t st) {
   hipLaunchKernelGGL(clip_factor_kernel, dim3(1), dim3(1), 0, st, sumsq, max_norm, out);
-  RET_LAST;
-}
-extern "C" int dbx_normalize_u8(const unsigned char* in, bf16* out, const unsigned char* flip, int N, int H, int W,
-                                int Cin, float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st) {
-  hipLaunchKernelGGL(normalize_u8_kernel, dim3(grid_for((long long)N * H * W)), dim3(256), 0, st, in, out, flip, N, H, W,
-                     Cin, m0, m1, m2, s0, s1, s2);
-  RET_LAST;
-}
-extern "C" int dbx_augment_u8(const unsigned char* in, bf16* out, const float* boxes, const unsigned char* flip, int N,
-                              int Hin, int Win, int Cin, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1,
-                              float s2, const int* perm, const int* mixbox, hipStream_t st) {
-  hipLaunchKernelGGL(augment_u8_kernel, dim3(N * Ho < 4096 ? N * Ho : 4096), dim3(Wo >= 256 ? 256 : ((Wo + 63) / 64) * 64), 0, st, in, out, boxes, flip, N,
-                     Hin, Win, Cin, Ho, Wo, m0, m1, m2, s0, s1, s2, perm, mixbox);
-  RET_LAST;
-}
-extern "C" int dbx_augment_mix_u8(const unsigned char* in, bf16* out, const float* boxes, const unsigned char* flip,
-                                  int N, int Hin, int Win, int Cin, int Ho, int Wo, float m0, float m1, float m2, float s0,
-                                  float s1, float s2, const int* perm, const int* mixbox, const float* blend,
-                                  const int* erase, int pixel, unsigned long long seed, const int* rng_offset,
-                                  hipStream_t st) {
-  const AugMix am{blend, erase, rng_offset, seed, pixel};
-  hipLaunchKernelGGL(augment_mix_u8_kernel, dim3(N * Ho < 4096 ? N * Ho : 4096), dim3(Wo >= 256 ? 256 : ((Wo + 63) / 64) * 64), 0, st, in, out, boxes, flip, N,
-                     Hin, Win, Cin, Ho, Wo, m0, m1, m2, s0, s1, s2, perm, mixbox, am);
   RET_LAST;
 }
 extern "C" int dbx_weight_prep(const float* master, bf16* wbuf, const void* desc_dev, int nlayers, hipStream_t st) {

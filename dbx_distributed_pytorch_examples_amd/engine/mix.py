@@ -75,7 +75,7 @@ def sample_erase_boxes(rng: np.random.Generator, n: int, H: int, W: int, prob: f
 
 AUTO_AUGMENTS = ("ta_wide",)
 TA_KINDS = 14  # Identity, ShearX, ShearY, TranslateX, TranslateY, Rotate, Brightness, Color, Contrast, Sharpness,
-#                Posterize, Solarize, AutoContrast, Equalize (ops/reference.py, csrc/ta_ops.hip)
+#                Posterize, Solarize, AutoContrast, Equalize (ops/reference.py, csrc/input_ops.hip)
 
 
 def validate_auto_augment(auto_augment=None, ta_num_bins=31) -> None:

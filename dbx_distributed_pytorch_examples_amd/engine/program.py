@@ -815,19 +815,18 @@ class ResNetProgram:
         std = self.norm_std or (IMAGENET_STD if self.in_ch == 3 else (0.5, 0.5, 0.5))
         if self.norm_mean and len(mean) == 1:
             mean, std = mean * 3, std * 3
-        mix = self.cutmix and self.training
-        if mix and self.ta_ops is not None:  # (evaluation never augments)
-            K.trivial_augment_u8(self.img_u8, self.x4, self.boxes, mean, std, self.flip if flip is None else flip,
-                                 self.ta_ops, self.ta_work, perm=self.mix_perm, mixbox=self.mix_box,
-                                 blend=self.mix_blend, erase=self.erase_box, erase_mode=self.erase_mode,
-                                 erase_rng=(self.erase_seed, self.erase_off))
-        elif mix and self.mix_blend is not None:
-            K.augment_u8(self.img_u8, self.x4, self.boxes, mean, std, self.flip if flip is None else flip,
-                         perm=self.mix_perm, mixbox=self.mix_box, blend=self.mix_blend, erase=self.erase_box,
-                         erase_mode=self.erase_mode, erase_rng=(self.erase_seed, self.erase_off))
+        mix = self.cutmix and self.training  # (evaluation never augments)
+        flip = self.flip if flip is None else flip
+        kw = {}
+        if mix:
+            kw = dict(perm=self.mix_perm, mixbox=self.mix_box)
+            if self.ta_ops is not None or self.mix_blend is not None:  # the mixing arena: blend, erasing
+                kw.update(blend=self.mix_blend, erase=self.erase_box, erase_mode=self.erase_mode,
+                          erase_rng=(self.erase_seed, self.erase_off))
+        if mix and self.ta_ops is not None:
+            K.trivial_augment_u8(self.img_u8, self.x4, self.boxes, mean, std, flip, self.ta_ops, self.ta_work, **kw)
         else:
-            K.augment_u8(self.img_u8, self.x4, self.boxes, mean, std, self.flip if flip is None else flip,
-                         perm=self.mix_perm if mix else None, mixbox=self.mix_box if mix else None)
+            K.augment_u8(self.img_u8, self.x4, self.boxes, mean, std, flip, **kw)
         if mix:  # the pasted samples' labels (device gather, inside the captured step)
             torch.index_select(self.labels, 0, self.mix_perm.long(), out=self.labels2)
 

@@ -1638,6 +1638,25 @@ def clip_factor(work, max_norm):
     return work[2:3]
 
 
+def _norm6(mean, std) -> Tuple[float, ...]:
+    """The six normalisation floats of the input kernels (csrc/input_ops.hip): mean[0..2], std[0..2]."""
+    return (float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]), float(std[2]))
+
+
+def _mix_args(N, perm, mixbox, blend, erase, erase_mode, erase_rng) -> tuple:
+    """The checked mixing options of ``augment_u8`` / ``ta_apply_u8`` as the kernels' trailing arguments
+    ``(perm, mixbox, blend, erase, pixel, seed, offset)``."""
+    seed, offset = _ref.check_augment_mix(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
+    for t, dt, nm, n in ((perm, torch.int32, "perm", N), (mixbox, torch.int32, "mixbox", 4),
+                         (blend, torch.float32, "blend", 1), (erase, torch.int32, "erase", N * 4)):
+        if t is not None:
+            _chk(t, dt, nm, n)
+    pixel = erase is not None and erase_mode == "pixel"
+    if pixel:
+        _chk(offset, torch.int32, "erase_rng offset", 1)
+    return (_p(perm), _p(mixbox), _p(blend), _p(erase), int(pixel), seed if pixel else 0, _p(offset) if pixel else 0)
+
+
 @_dispatch
 def normalize_u8(img, out, mean, std, flip=None):
     N, H, W, Cin = img.shape
@@ -1645,8 +1664,7 @@ def normalize_u8(img, out, mean, std, flip=None):
     _chk(out, torch.bfloat16, "out", N * H * W * 4)
     if flip is not None:
         _chk(flip, torch.uint8, "flip", N)
-    C().normalize_u8(img.data_ptr(), out.data_ptr(), _p(flip), N, H, W, Cin, float(mean[0]), float(mean[1]),
-                     float(mean[2]), float(std[0]), float(std[1]), float(std[2]), stream_ptr())
+    C().normalize_u8(img.data_ptr(), out.data_ptr(), _p(flip), N, H, W, Cin, *_norm6(mean, std), stream_ptr())
 
 
 @_dispatch
@@ -1673,26 +1691,12 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *,
     _chk(boxes, torch.float32, "boxes", N * 4)
     if flip is not None:
         _chk(flip, torch.uint8, "flip", N)
-    seed, offset = _ref.check_augment_mix(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
-    if perm is not None:
-        _chk(perm, torch.int32, "perm", N)
-    if mixbox is not None:
-        _chk(mixbox, torch.int32, "mixbox", 4)
-    norm = (float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]), float(std[2]))
+    mix = _mix_args(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
+    args = (img.data_ptr(), out.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Cin, Ho, Wo, *_norm6(mean, std))
     if blend is None and erase is None:
-        C().augment_u8(img.data_ptr(), out.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Cin, Ho, Wo,
-                       *norm, _p(perm), _p(mixbox), stream_ptr())
-        return
-    if blend is not None:
-        _chk(blend, torch.float32, "blend", 1)
-    pixel = erase is not None and erase_mode == "pixel"
-    if erase is not None:
-        _chk(erase, torch.int32, "erase", N * 4)
-    if pixel:
-        _chk(offset, torch.int32, "erase_rng offset", 1)
-    C().augment_mix_u8(img.data_ptr(), out.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Cin, Ho, Wo,
-                       *norm, _p(perm), _p(mixbox), _p(blend), _p(erase), int(pixel), seed if pixel else 0,
-                       _p(offset) if pixel else 0, stream_ptr())
+        C().augment_u8(*args, *mix[:2], stream_ptr())
+    else:
+        C().augment_mix_u8(*args, *mix, stream_ptr())
 
 
 ta_work_words = _ref.ta_work_words  # int32 words of trivial_augment_u8's work buffer for (N, Ho, Wo)
@@ -1750,18 +1754,9 @@ def ta_apply_u8(T, out, ops, lut, tmean, mean, std, *, perm=None, mixbox=None, b
     _chk(tmean, torch.int32, "tmean", N)
     if C4 != 4 or T.data_ptr() % 4 or lut.data_ptr() % 4:
         raise ValueError("T: expected [N, Ho, Wo, 4] uint8; T and lut 4-byte aligned")
-    seed, offset = _ref.check_augment_mix(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
-    for t, dt, nm, n in ((perm, torch.int32, "perm", N), (mixbox, torch.int32, "mixbox", 4),
-                         (blend, torch.float32, "blend", 1), (erase, torch.int32, "erase", N * 4)):
-        if t is not None:
-            _chk(t, dt, nm, n)
-    pixel = erase is not None and erase_mode == "pixel"
-    if pixel:
-        _chk(offset, torch.int32, "erase_rng offset", 1)
+    mix = _mix_args(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
     C().ta_apply_u8(T.data_ptr(), out.data_ptr(), ops.data_ptr(), lut.data_ptr(), tmean.data_ptr(), N, Ho, Wo,
-                    float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]), float(std[2]),
-                    _p(perm), _p(mixbox), _p(blend), _p(erase), int(pixel), seed if pixel else 0,
-                    _p(offset) if pixel else 0, stream_ptr())
+                    *_norm6(mean, std), *mix, stream_ptr())
 
 
 def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None, erase=None,

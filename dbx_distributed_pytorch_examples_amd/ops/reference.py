@@ -823,7 +823,7 @@ def _augment_v255(img, Ho, Wo, boxes, flip=None):
 
 
 # ---------------------------------------------------------------------------------------------
-# TrivialAugmentWide (csrc/ta_ops.hip): one of fourteen operations per sample on the uint8 image after
+# TrivialAugmentWide (csrc/input_ops.hip): one of fourteen operations per sample on the uint8 image after
 # crop / resize / flip and before normalisation, erasing and batch mixing. Everything here is integer
 # or fixed-order fp32 (AutoContrast: float64) arithmetic, so the kernels match it bit for bit, and it
 # matches Pillow (the library torchvision calls for these operations) bit for bit except at rotation

@@ -1,5 +1,5 @@
 """Per-element checks of ``augment_u8``'s mixing options: the MixUp blend, random erasing ("const" and
-"pixel") and their combination with the CutMix paste (csrc/nn_ops.hip augment_mix_u8_kernel).
+"pixel") and their combination with the CutMix paste (csrc/input_ops.hip augment_mix_u8_kernel).
 
 The rules are those of tests/test_nn_ops.py, whose helpers are imported: every test runs on the CPU
 (``ops/reference.py``, the dispatcher's CPU path) and on the GPU (the HIP kernel); the oracle is float64
@@ -29,7 +29,7 @@ import torch
 
 from dbx_distributed_pytorch_examples_amd.ops import kernels as K
 from dbx_distributed_pytorch_examples_amd.ops import reference as R
-from test_nn_ops import (AUG_CASES, BF, DEVICES, F32, GPU_ONLY, MEAN, RATIOS, STD, G, _augment_ref, _norm_ref,
+from test_nn_ops import (AUG_CASES, AUG_STAGED, BF, DEVICES, F32, GPU_ONLY, MEAN, RATIOS, STD, G, _augment_ref, _norm_ref,
                          bf16_bound, check, gen)
 
 devices = pytest.mark.parametrize("dev", DEVICES)
@@ -38,8 +38,7 @@ FLIPS = [0, 1, 1]
 PERMS = [pytest.param([2, 0, 1], id="perm201"), pytest.param([0, 2, 1], id="perm021-fixed-point")]
 # the three unstaged shapes of test_nn_ops (an odd row length, a row longer than 4096 bytes) and a staged one
 # (96-byte rows: a multiple of 16 from a 16-byte aligned base)
-CASES = AUG_CASES + [pytest.param(32, 3, 9, [(-1.25, -2.5, 16, 16), (0.75, 3.25, 8, 16), (2.0, 14.25, 4, 16)],
-                                  id="W32-C3-staged")]
+CASES = AUG_CASES + [AUG_STAGED]
 cases = pytest.mark.parametrize("Win,Cin,Hin,boxes", CASES)
 # boxes whose source coordinates are NOT exact in fp32: only for comparing two calls bit for bit
 INEXACT = [(0.3, 1.7, 7.1, 23.3), (1.1, 0.2, 5.9, 29.9), (0.0, 3.3, 8.7, 11.3)]

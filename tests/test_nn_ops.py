@@ -1,4 +1,4 @@
-"""Per-element checks of the memory-bound kernels (csrc/nn_ops.hip) at every width and option.
+"""Per-element checks of the memory-bound kernels (csrc/nn_ops.hip, csrc/input_ops.hip) at every width and option.
 
 Every test runs on the CPU (``ops.kernels`` dispatches CPU tensors to ``ops/reference.py``, so the
 test's own logic and bounds are checked without a GPU, and the reference path is pinned) and on the
@@ -978,14 +978,17 @@ AUG_CASES = [
     pytest.param(30, 1, 9, [(-1.25, -2.5, 16, 16), (0.75, 3.25, 8, 16), (2.0, 20.25, 4, 16)], id="W30-C1"),
     pytest.param(1400, 3, 5, [(-0.5, 300.25, 4, 1024), (0.25, -8.0, 8, 2048), (1.0, 1390.5, 4, 16)], id="W1400-C3"),
 ]
+# 96-byte rows from a 16-byte aligned base: the two source rows go through LDS
+AUG_STAGED = pytest.param(32, 3, 9, [(-1.25, -2.5, 16, 16), (0.75, 3.25, 8, 16), (2.0, 14.25, 4, 16)], id="W32-C3-staged")
 
 
 @pytest.mark.parametrize("cutmix", [False, True])
-@pytest.mark.parametrize("Win,Cin,Hin,boxes", AUG_CASES)
+@pytest.mark.parametrize("Win,Cin,Hin,boxes", AUG_CASES + [AUG_STAGED])
 @devices
 def test_augment_u8(dev, Win, Cin, Hin, boxes, cutmix):
-    """The non-staged path (rows whose byte length is no multiple of 16, or longer than 4096 bytes),
-    with flips, and a CutMix box that touches the top and right image edges."""
+    """The non-staged path (rows whose byte length is no multiple of 16, or longer than 4096 bytes) and the
+    staged one (with cutmix: both passes of a row reuse the staged rows), with flips, and a CutMix box that
+    touches the top and right image edges."""
     N, Ho, Wo = 3, 8, 8
     g = gen(dev, 20)
     img = torch.randint(0, 256, (N, Hin, Win, Cin), generator=g, device=dev, dtype=torch.uint8)

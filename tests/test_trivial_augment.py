@@ -1,4 +1,4 @@
-"""Per-element checks of the TrivialAugmentWide input kernels (csrc/ta_ops.hip): ``crop_resize_u8``,
+"""Per-element checks of the TrivialAugmentWide input kernels (csrc/input_ops.hip): ``crop_resize_u8``,
 ``ta_prepare``, ``ta_apply_u8`` and the composed ``trivial_augment_u8``.
 
 The rules are those of tests/test_nn_ops.py and tests/test_augment_mix.py, whose helpers are imported:
@@ -22,7 +22,7 @@ from dbx_distributed_pytorch_examples_amd.engine import mix as M
 from dbx_distributed_pytorch_examples_amd.ops import kernels as K
 from dbx_distributed_pytorch_examples_amd.ops import reference as R
 from test_augment_mix import INEXACT, PERMS, i32, noise64, oracle
-from test_nn_ops import (AUG_CASES, BF, DEVICES, F32, GPU_ONLY, MEAN, RATIOS, STD, G, _augment_ref, _norm_ref,
+from test_nn_ops import (AUG_CASES, AUG_STAGED, BF, DEVICES, F32, GPU_ONLY, MEAN, RATIOS, STD, G, _augment_ref, _norm_ref,
                          bf16_bound, check, gen)
 
 devices = pytest.mark.parametrize("dev", DEVICES)
@@ -173,6 +173,36 @@ def test_augmented_samples_travel(dev, Ho, Wo, perm, mix, erase_mode):
             check("trivial_augment travels", dev, got[..., :3], ref, bf16_bound(ref, m), what=f"{mix} {erase_mode}")
 
 
+@devices
+def test_row_wider_than_one_tile(dev):
+    """1030 columns: ta_apply_u8 walks a row in tiles of 1024, and the paste box, the blend and the erase box
+    all reach into the second tile, with a gather across rows and a LUT kind in the table. Image levels are
+    multiples of 4 (Posterize keeps multiples of 8) and w = 1/4, so every blended value is an integer below 256,
+    exact in bf16 and far from a rounding boundary: the kernel's unit normalisation (v * 1/(255 std), exactly v)
+    and the reference's ((v / 255) / std, within 2^-22 of v) round to the same bits, whatever the order of the
+    blend's roundings. The output equals ``reference.ta_apply_u8`` bit for bit -- on the CPU that is the function
+    under test itself, so there only the assertions against ``definition()`` below carry weight."""
+    n, Ho, Wo = 2, 3, 1030
+    rs = np.random.default_rng(7)
+    rgb = (4 * rs.integers(0, 64, (n, Ho, Wo, 3))).astype(np.uint8)
+    rows = table([(5, 0.1), (10, 5.0)], Ho, Wo)  # Rotate by 0.1 degrees (0.9 rows at the row ends), Posterize
+    T, ops, lut, tmean = prepared(rgb, rows, "cpu")
+    kw = dict(perm=[1, 0], mixbox=[0, 2, 1000, 1030], blend=[0.25], erase=[(1, 3, 1020, 1028), (0, 0, 0, 0)])
+    tens = lambda d: dict(perm=i32(kw["perm"], d), mixbox=i32(kw["mixbox"], d), erase=i32(kw["erase"], d),  # noqa: E731
+                          blend=torch.tensor(kw["blend"], dtype=F32, device=d), erase_mode="const")
+    want = torch.full((n, Ho, Wo, 4), float("nan"), dtype=BF)
+    R.ta_apply_u8(T, want, ops, lut, tmean, *UNIT, **tens("cpu"))
+    got = apply(dev, T.to(dev), ops.to(dev), lut.to(dev), tmean.to(dev), **tens(dev))
+    assert torch.equal(got.cpu(), want)
+    # (not vacuous: the second tile holds pasted, blended and erased pixels)
+    aug = torch.from_numpy(definition(rgb, rows)).double()
+    assert bool((aug[0, :, 1024:] != torch.from_numpy(rgb)[0, :, 1024:]).any()) and bool(aug[0, :, 1024:].any())
+    assert torch.equal(want[1, 0, 1024:, :3].double(), aug[0, 0, 1024:])       # pasted from sample 0
+    assert torch.equal(want[1, 1, 1020:1028, :3].double(), torch.zeros(8, 3))  # ... with its erase box
+    assert torch.equal(want[0, 2, 1024:1028, :3], (0.75 * aug[1, 2, 1024:1028]).to(BF))  # erased, then blended
+    assert torch.equal(want[0, 2, 1028:, :3], (0.25 * aug[0, 2, 1028:] + 0.75 * aug[1, 2, 1028:]).to(BF))
+
+
 # ---------------------------------------------------------------------------------------------
 # 3. ta_prepare
 # ---------------------------------------------------------------------------------------------
@@ -210,8 +240,7 @@ def test_ta_prepare(dev, name, img):
 # ---------------------------------------------------------------------------------------------
 # 4. crop_resize_u8
 # ---------------------------------------------------------------------------------------------
-C3_CASES = [c for c in AUG_CASES if c.values[1] == 3] + [
-    pytest.param(32, 3, 9, [(-1.25, -2.5, 16, 16), (0.75, 3.25, 8, 16), (2.0, 14.25, 4, 16)], id="W32-C3-staged")]
+C3_CASES = [c for c in AUG_CASES if c.values[1] == 3] + [AUG_STAGED]
 
 
 def crop(dev, img, bx, fl, Ho, Wo):
