@@ -55,33 +55,18 @@ int dbx_avgpool_bwd(const bf16*, bf16*, int, int, int, hipStream_t);
 int dbx_softmax_ce(const void*, int, const long long*, void*, float*, double*, int, int, float, float,
                    const long long*, const float*, hipStream_t);
 int dbx_sgd(float*, const float*, float*, bf16*, long long, const float*, float, float, float, float, int, int,
-            const float*, float, hipStream_t);
+            const float*, float, float*, const float*, float, const int*, int, long long, hipStream_t);
 int dbx_adam(float*, const float*, float*, float*, bf16*, long long, const float*, float, float, float, float, float, int,
-             float, float, const float*, float, hipStream_t);
+             float, float, const float*, float, float*, const float*, float, const int*, int, long long, hipStream_t);
 int dbx_grad_accum(float*, const float*, long long, int, const float*, hipStream_t);
-int dbx_sgd_ema(float*, const float*, float*, bf16*, long long, const float*, float, float, float, float, int, int,
-                const float*, float, float*, const float*, float, hipStream_t);
-int dbx_adam_ema(float*, const float*, float*, float*, bf16*, long long, const float*, float, float, float, float, float,
-                 int, float, float, const float*, float, float*, const float*, float, hipStream_t);
-int dbx_sgd_groups(float*, const float*, float*, bf16*, long long, const float*, float, float, float, int, int,
-                   const float*, float, const int*, int, long long, hipStream_t);
-int dbx_sgd_groups_ema(float*, const float*, float*, bf16*, long long, const float*, float, float, float, int, int,
-                       const float*, float, const int*, int, long long, float*, const float*, float, hipStream_t);
-int dbx_adam_groups(float*, const float*, float*, float*, bf16*, long long, const float*, float, float, float, float,
-                    int, float, float, const float*, float, const int*, int, long long, hipStream_t);
-int dbx_adam_groups_ema(float*, const float*, float*, float*, bf16*, long long, const float*, float, float, float,
-                        float, int, float, float, const float*, float, const int*, int, long long, float*,
-                        const float*, float, hipStream_t);
 int dbx_ema_update(float*, const float*, long long, const float*, float, hipStream_t);
 int dbx_ema_update_multi(const void*, int, long long, const float*, float, hipStream_t);
 int dbx_sumsq(const float*, long long, double*, hipStream_t);
 int dbx_lars_scale(const float*, float*, const int*, const int*, const int*, int, int, double*, float, float, float,
                    hipStream_t);
 int dbx_lamb(float*, float*, float*, float*, bf16*, const int*, const int*, const int*, int, int, double*, const float*,
-             float, float, float, float, float, float, float, float, float, const float*, float, hipStream_t);
-int dbx_lamb_ema(float*, float*, float*, float*, bf16*, const int*, const int*, const int*, int, int, double*,
-                 const float*, float, float, float, float, float, float, float, float, float, const float*, float,
-                 float*, const float*, float, hipStream_t);
+             float, float, float, float, float, float, float, float, float, const float*, float, float*, const float*,
+             float, hipStream_t);
 int dbx_clip_factor(const double*, float, float*, hipStream_t);
 int dbx_normalize_u8(const unsigned char*, bf16*, const unsigned char*, int, int, int, int, float, float, float, float,
                      float, float, hipStream_t);
@@ -336,16 +321,20 @@ PYBIND11_MODULE(_C, m) {
           "softmax_ce");
   });
   m.def("sgd", [](uintptr_t p, uintptr_t g, uintptr_t v, uintptr_t p16, long long n, uintptr_t hyper, float lr,
-                  float mom, float damp, float wd, int nesterov, int first, uintptr_t gsp, float gs, uintptr_t st) {
+                  float mom, float damp, float wd, int nesterov, int first, uintptr_t gsp, float gs, uintptr_t ema,
+                  uintptr_t omd_ptr, float omd, uintptr_t tab, int nruns, long long run_base, uintptr_t st) {
     check(dbx_sgd(P<float*>(p), P<const float*>(g), P<float*>(v), P<bf16*>(p16), n, P<const float*>(hyper), lr, mom,
-                  damp, wd, nesterov, first, P<const float*>(gsp), gs, S(st)),
+                  damp, wd, nesterov, first, P<const float*>(gsp), gs, P<float*>(ema), P<const float*>(omd_ptr), omd,
+                  P<const int*>(tab), nruns, run_base, S(st)),
           "sgd");
   });
   m.def("adam", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t p16, long long n, uintptr_t hyper,
                    float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2, uintptr_t gsp,
-                   float gs, uintptr_t st) {
+                   float gs, uintptr_t ema, uintptr_t omd_ptr, float omd, uintptr_t tab, int nruns, long long run_base,
+                   uintptr_t st) {
     check(dbx_adam(P<float*>(p), P<const float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(p16), n,
-                   P<const float*>(hyper), lr, b1, b2, eps, wd, decoupled, bc1, bc2, P<const float*>(gsp), gs, S(st)),
+                   P<const float*>(hyper), lr, b1, b2, eps, wd, decoupled, bc1, bc2, P<const float*>(gsp), gs,
+                   P<float*>(ema), P<const float*>(omd_ptr), omd, P<const int*>(tab), nruns, run_base, S(st)),
           "adam");
   });
   m.def("lars_scale", [](uintptr_t p, uintptr_t g, uintptr_t off, uintptr_t len, uintptr_t adapt, int nseg, int max_len,
@@ -357,72 +346,12 @@ PYBIND11_MODULE(_C, m) {
   m.def("lamb", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t p16, uintptr_t off, uintptr_t len,
                    uintptr_t adapt, int nseg, int max_len, uintptr_t norms, uintptr_t hyper, float lr, float b1, float b2,
                    float eps, float wd, float bc1, float bc2, float tmin, float tmax, uintptr_t gsp, float gs,
-                   uintptr_t st) {
+                   uintptr_t ema, uintptr_t omd_ptr, float omd, uintptr_t st) {
     check(dbx_lamb(P<float*>(p), P<float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(p16), P<const int*>(off),
                    P<const int*>(len), P<const int*>(adapt), nseg, max_len, P<double*>(norms), P<const float*>(hyper),
-                   lr, b1, b2, eps, wd, bc1, bc2, tmin, tmax, P<const float*>(gsp), gs, S(st)),
+                   lr, b1, b2, eps, wd, bc1, bc2, tmin, tmax, P<const float*>(gsp), gs, P<float*>(ema),
+                   P<const float*>(omd_ptr), omd, S(st)),
           "lamb");
-  });
-  m.def("lamb_ema", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t p16, uintptr_t off, uintptr_t len,
-                       uintptr_t adapt, int nseg, int max_len, uintptr_t norms, uintptr_t hyper, float lr, float b1,
-                       float b2, float eps, float wd, float bc1, float bc2, float tmin, float tmax, uintptr_t gsp,
-                       float gs, uintptr_t ema, uintptr_t omd_ptr, float omd, uintptr_t st) {
-    check(dbx_lamb_ema(P<float*>(p), P<float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(p16), P<const int*>(off),
-                       P<const int*>(len), P<const int*>(adapt), nseg, max_len, P<double*>(norms),
-                       P<const float*>(hyper), lr, b1, b2, eps, wd, bc1, bc2, tmin, tmax, P<const float*>(gsp), gs,
-                       P<float*>(ema), P<const float*>(omd_ptr), omd, S(st)),
-          "lamb_ema");
-  });
-  m.def("sgd_ema", [](uintptr_t p, uintptr_t g, uintptr_t v, uintptr_t p16, long long n, uintptr_t hyper, float lr,
-                      float mom, float damp, float wd, int nesterov, int first, uintptr_t gsp, float gs, uintptr_t ema,
-                      uintptr_t omd_ptr, float omd, uintptr_t st) {
-    check(dbx_sgd_ema(P<float*>(p), P<const float*>(g), P<float*>(v), P<bf16*>(p16), n, P<const float*>(hyper), lr, mom,
-                      damp, wd, nesterov, first, P<const float*>(gsp), gs, P<float*>(ema), P<const float*>(omd_ptr),
-                      omd, S(st)),
-          "sgd_ema");
-  });
-  m.def("adam_ema", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t p16, long long n, uintptr_t hyper,
-                       float lr, float b1, float b2, float eps, float wd, int decoupled, float bc1, float bc2,
-                       uintptr_t gsp, float gs, uintptr_t ema, uintptr_t omd_ptr, float omd, uintptr_t st) {
-    check(dbx_adam_ema(P<float*>(p), P<const float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(p16), n,
-                       P<const float*>(hyper), lr, b1, b2, eps, wd, decoupled, bc1, bc2, P<const float*>(gsp), gs,
-                       P<float*>(ema), P<const float*>(omd_ptr), omd, S(st)),
-          "adam_ema");
-  });
-  m.def("sgd_groups", [](uintptr_t p, uintptr_t g, uintptr_t v, uintptr_t p16, long long n, uintptr_t hyper, float lr,
-                         float mom, float damp, int nesterov, int first, uintptr_t gsp, float gs, uintptr_t tab,
-                         int nruns, long long run_base, uintptr_t st) {
-    check(dbx_sgd_groups(P<float*>(p), P<const float*>(g), P<float*>(v), P<bf16*>(p16), n, P<const float*>(hyper), lr,
-                         mom, damp, nesterov, first, P<const float*>(gsp), gs, P<const int*>(tab), nruns, run_base,
-                         S(st)),
-          "sgd_groups");
-  });
-  m.def("sgd_groups_ema", [](uintptr_t p, uintptr_t g, uintptr_t v, uintptr_t p16, long long n, uintptr_t hyper,
-                             float lr, float mom, float damp, int nesterov, int first, uintptr_t gsp, float gs,
-                             uintptr_t tab, int nruns, long long run_base, uintptr_t ema, uintptr_t omd_ptr, float omd,
-                             uintptr_t st) {
-    check(dbx_sgd_groups_ema(P<float*>(p), P<const float*>(g), P<float*>(v), P<bf16*>(p16), n, P<const float*>(hyper),
-                             lr, mom, damp, nesterov, first, P<const float*>(gsp), gs, P<const int*>(tab), nruns,
-                             run_base, P<float*>(ema), P<const float*>(omd_ptr), omd, S(st)),
-          "sgd_groups_ema");
-  });
-  m.def("adam_groups", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t p16, long long n,
-                          uintptr_t hyper, float lr, float b1, float b2, float eps, int decoupled, float bc1, float bc2,
-                          uintptr_t gsp, float gs, uintptr_t tab, int nruns, long long run_base, uintptr_t st) {
-    check(dbx_adam_groups(P<float*>(p), P<const float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(p16), n,
-                          P<const float*>(hyper), lr, b1, b2, eps, decoupled, bc1, bc2, P<const float*>(gsp), gs,
-                          P<const int*>(tab), nruns, run_base, S(st)),
-          "adam_groups");
-  });
-  m.def("adam_groups_ema", [](uintptr_t p, uintptr_t g, uintptr_t mm, uintptr_t v, uintptr_t p16, long long n,
-                              uintptr_t hyper, float lr, float b1, float b2, float eps, int decoupled, float bc1,
-                              float bc2, uintptr_t gsp, float gs, uintptr_t tab, int nruns, long long run_base,
-                              uintptr_t ema, uintptr_t omd_ptr, float omd, uintptr_t st) {
-    check(dbx_adam_groups_ema(P<float*>(p), P<const float*>(g), P<float*>(mm), P<float*>(v), P<bf16*>(p16), n,
-                              P<const float*>(hyper), lr, b1, b2, eps, decoupled, bc1, bc2, P<const float*>(gsp), gs,
-                              P<const int*>(tab), nruns, run_base, P<float*>(ema), P<const float*>(omd_ptr), omd,
-                              S(st)),
-          "adam_groups_ema");
   });
   m.def("ema_update", [](uintptr_t e, uintptr_t p, long long n, uintptr_t omd_ptr, float omd, uintptr_t st) {
     check(dbx_ema_update(P<float*>(e), P<const float*>(p), n, P<const float*>(omd_ptr), omd, S(st)), "ema_update");

@@ -100,6 +100,15 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
 }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
+// blocks of an elementwise grid-stride launch over n items: ceil(n / block), at least 1, at most cap
+static inline int grid_for(long long n, int block = 256, int cap = 8192) {
+  long long g = (n + block - 1) / block;
+  if (g < 1) g = 1;
+  if (g > cap) g = cap;
+  return (int)g;
+}
+// the last statement of a C ABI launcher: the launch's error code
+#define RET_LAST return (int)hipGetLastError()
 
 // Raw buffer loads (SRD in SGPRs, 32-bit per-lane byte offset). An offset at or past num_records
 // returns zeros, which is how the conv gathers zero-fill padding taps and rows past M without a

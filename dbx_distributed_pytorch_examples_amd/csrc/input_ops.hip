@@ -588,7 +588,6 @@ __global__ __launch_bounds__(256) void ta_apply_u8_kernel(const unsigned* __rest
 }  // namespace dbx
 
 using namespace dbx;
-#define RET_LAST return (int)hipGetLastError()
 
 // one block per output row (crop_resize_u8: per chunk of rows), at most 4096; a wave per 64 output columns
 static inline dim3 row_grid(long long rows) { return dim3((unsigned)(rows < 4096 ? rows : 4096)); }

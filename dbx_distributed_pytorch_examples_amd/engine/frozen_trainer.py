@@ -132,13 +132,8 @@ class NativeHead:
     def optimizer(self) -> None:
         K, o = self.K, self.o
         gs = 1.0 / self.world
-        if o.name == "sgd":
-            K.sgd_step(self.master, self.grad, self.m, self.p16, lr=o.lr, momentum=o.momentum,
-                       weight_decay=o.weight_decay, nesterov=o.nesterov, first=False, grad_scale=gs, hyper=self.hyper)
-        else:
-            K.adam_step(self.master, self.grad, self.m, self.v, self.p16, lr=o.lr, beta1=o.betas[0], beta2=o.betas[1],
-                        eps=o.eps, weight_decay=o.weight_decay, decoupled=(o.name == "adamw"), step=self.step_count,
-                        grad_scale=gs, hyper=self.hyper)
+        K.optim_step(o, self.master, self.grad, self.m, self.v, self.p16, step=self.step_count, grad_scale=gs,
+                     hyper=self.hyper)
         self.drop_off.add_(1)  # the next step's dropout mask
 
     @torch.no_grad()

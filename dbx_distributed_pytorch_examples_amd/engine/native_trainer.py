@@ -490,18 +490,13 @@ class NativeTrainer:
             return None
         return {"per_phase": per, "gaps": gaps}
 
-    def _update_range(self, lo: int, hi: int):
-        p, o = self.prog, self.opt
-        gscale = 1.0 / (self.world * self.loopback * self.k)
-        if o.name == "sgd":
-            K.sgd_step(p.master[lo:hi], p.grad[lo:hi], self.mom[lo:hi], None, lr=o.lr, momentum=o.momentum,
-                       dampening=o.dampening, nesterov=o.nesterov, first=False,
-                       grad_scale=gscale, hyper=self.hyper, **self._wd_kw(lo), **self._ema_kw(lo, hi))
-        else:
-            K.adam_step(p.master[lo:hi], p.grad[lo:hi], self.mom[lo:hi], self.mom2[lo:hi], None, lr=o.lr,
-                        beta1=o.betas[0], beta2=o.betas[1], eps=o.eps, **self._wd_kw(lo),
-                        decoupled=(o.name == "adamw"), step=1, grad_scale=gscale, hyper=self.hyper,
-                        **self._ema_kw(lo, hi))
+    def _update_range(self, lo: int, hi: int, gsp=None):
+        """The SGD / Adam update of master[lo:hi] from the reduced gradient sum (``gsp``: the clip factor)."""
+        p = self.prog
+        K.optim_step(self.opt, p.master[lo:hi], p.grad[lo:hi], self.mom[lo:hi],
+                     None if self.mom2 is None else self.mom2[lo:hi], grad_scale_ptr=gsp,
+                     grad_scale=1.0 / (self.world * self.loopback * self.k), hyper=self.hyper,
+                     **self._wd_kw(lo), **self._ema_kw(lo, hi))
 
     def _after_phase_updates(self, i: int):
         """Issue phase i's parameter updates (see _optimizer_ranges)."""
@@ -611,9 +606,8 @@ class NativeTrainer:
             off, ln, adapt, norms, mx = self.lars
             K.lars_scale(p.master, p.grad, off, ln, adapt, norms, grad_scale=1.0 / gdiv,
                          eta=o.trust_coefficient, weight_decay=o.weight_decay, max_len=mx)
-            K.sgd_step(p.master, p.grad, self.mom, None, lr=o.lr, momentum=o.momentum, dampening=o.dampening,
-                       weight_decay=0.0, nesterov=o.nesterov, first=False, grad_scale=1.0, hyper=self.hyper,
-                       **self._ema_kw(0, p.n_params))
+            K.optim_step(o, p.master, p.grad, self.mom, None, weight_decay=0.0, grad_scale=1.0, hyper=self.hyper,
+                         **self._ema_kw(0, p.n_params))
             return
         gscale = 1.0 / gdiv
         if self.lamb is not None:
@@ -625,14 +619,7 @@ class NativeTrainer:
                         trust_min=o.trust_min, trust_max=o.trust_max, grad_scale_ptr=gsp, grad_scale=gscale,
                         hyper=self.hyper, max_len=mx, **self._ema_kw(0, p.n_params))
             return
-        if o.name == "sgd":
-            K.sgd_step(p.master, p.grad, self.mom, None, lr=o.lr, momentum=o.momentum, dampening=o.dampening,
-                       nesterov=o.nesterov, first=False, grad_scale_ptr=gsp,
-                       grad_scale=gscale, hyper=self.hyper, **self._wd_kw(0), **self._ema_kw(0, p.n_params))
-        else:
-            K.adam_step(p.master, p.grad, self.mom, self.mom2, None, lr=o.lr, beta1=o.betas[0], beta2=o.betas[1],
-                        eps=o.eps, **self._wd_kw(0), decoupled=(o.name == "adamw"), step=1,
-                        grad_scale_ptr=gsp, grad_scale=gscale, hyper=self.hyper, **self._ema_kw(0, p.n_params))
+        self._update_range(0, p.n_params, gsp)
 
     # ----------------------------------------------------------------------------------
     def _post(self, post):

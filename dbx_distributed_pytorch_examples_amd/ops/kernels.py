@@ -1357,14 +1357,17 @@ def dropout(x, y, p, seed, offset):
     return y
 
 
-OPT_MAX_RUNS = _ref.OPT_MAX_RUNS  # csrc/nn_ops.hip kOptMaxRuns
+OPT_MAX_RUNS = _ref.OPT_MAX_RUNS  # csrc/optim_ops.hip kOptMaxRuns
 pack_opt_runs = _ref.pack_opt_runs
 
 
-def _chk_opt_runs(runs, n: int, run_base: int, weight_decay: float, what: str, f32, p16) -> Tuple[int, int, int]:
-    """A grouped launch's host checks: the table (validated once per tensor object, see
+def _runs_args(runs, n: int, run_base: int, weight_decay: float, what: str, f32, p16) -> Tuple[int, int, int]:
+    """The (table, nruns, run_base) arguments of an SGD / Adam launch, zeros without ``runs``. A grouped
+    launch's host checks: the table (validated once per tensor object, see
     ``reference.check_opt_runs``; never read back by a captured or replayed step), the slice inside it, and
     the alignment :func:`lamb_step` asks for (16 bytes per lane from every base)."""
+    if runs is None:
+        return 0, 0, 0
     starts, _, _ = _ref.check_opt_runs(runs, n, run_base, weight_decay, what)
     if runs.device != f32[0][0].device:
         raise ValueError(f"{what}: runs is on {runs.device}, p on {f32[0][0].device}")
@@ -1392,24 +1395,10 @@ def sgd_step(p, g, v, p16=None, *, lr, momentum, dampening=0.0, weight_decay=0.0
     _chk(v, torch.float32, "v", n)
     if p16 is not None:
         _chk(p16, torch.bfloat16, "p16", n)
-    if runs is not None:
-        tab = _chk_opt_runs(runs, n, run_base, weight_decay, "sgd_step", ((p, "p"), (g, "g"), (v, "v")), p16)
-        args = (p.data_ptr(), g.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr), float(momentum),
-                float(dampening), int(nesterov), int(first), _p(grad_scale_ptr), float(grad_scale), *tab)
-        if ema is not None:
-            _chk_ema(ema, n, ema_hyper)
-            C().sgd_groups_ema(*args, ema.data_ptr(), _p(ema_hyper), float(ema_one_minus_decay), stream_ptr())
-            return
-        C().sgd_groups(*args, stream_ptr())
-        return
-    if ema is not None:
-        _chk_ema(ema, n, ema_hyper)
-        C().sgd_ema(p.data_ptr(), g.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr), float(momentum),
-                    float(dampening), float(weight_decay), int(nesterov), int(first), _p(grad_scale_ptr),
-                    float(grad_scale), ema.data_ptr(), _p(ema_hyper), float(ema_one_minus_decay), stream_ptr())
-        return
+    tab = _runs_args(runs, n, run_base, weight_decay, "sgd_step", ((p, "p"), (g, "g"), (v, "v")), p16)
     C().sgd(p.data_ptr(), g.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr), float(momentum), float(dampening),
-            float(weight_decay), int(nesterov), int(first), _p(grad_scale_ptr), float(grad_scale), stream_ptr())
+            float(weight_decay), int(nesterov), int(first), _p(grad_scale_ptr), float(grad_scale),
+            *_ema_args(ema, n, ema_hyper, ema_one_minus_decay), *tab, stream_ptr())
 
 
 def reject_dampening(optim) -> None:
@@ -1421,7 +1410,7 @@ def reject_dampening(optim) -> None:
                          "the first step would be damped, unlike torch.optim.SGD); use dampening=0")
 
 
-LARS_MAX_BLOCKS = 64  # csrc/nn_ops.hip kLarsMaxBlocks
+LARS_MAX_BLOCKS = 64  # csrc/optim_ops.hip kLarsMaxBlocks
 
 
 @_dispatch
@@ -1454,30 +1443,31 @@ def adam_step(p, g, m, v, p16=None, *, lr, beta1, beta2, eps, weight_decay, deco
         _chk(t, torch.float32, nm, n)
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
-    if runs is not None:
-        if p16 is not None:
-            _chk(p16, torch.bfloat16, "p16", n)
-        tab = _chk_opt_runs(runs, n, run_base, weight_decay, "adam_step",
-                            ((p, "p"), (g, "g"), (m, "m"), (v, "v")), p16)
-        args = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr),
-                float(beta1), float(beta2), float(eps), int(decoupled), float(bc1), float(bc2), _p(grad_scale_ptr),
-                float(grad_scale), *tab)
-        if ema is not None:
-            _chk_ema(ema, n, ema_hyper)
-            C().adam_groups_ema(*args, ema.data_ptr(), _p(ema_hyper), float(ema_one_minus_decay), stream_ptr())
-            return
-        C().adam_groups(*args, stream_ptr())
-        return
-    if ema is not None:
-        _chk_ema(ema, n, ema_hyper)
-        C().adam_ema(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr),
-                     float(beta1), float(beta2), float(eps), float(weight_decay), int(decoupled), float(bc1),
-                     float(bc2), _p(grad_scale_ptr), float(grad_scale), ema.data_ptr(), _p(ema_hyper),
-                     float(ema_one_minus_decay), stream_ptr())
-        return
+    if runs is not None and p16 is not None:
+        _chk(p16, torch.bfloat16, "p16", n)
+    tab = _runs_args(runs, n, run_base, weight_decay, "adam_step", ((p, "p"), (g, "g"), (m, "m"), (v, "v")), p16)
     C().adam(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p16), n, _p(hyper), float(lr), float(beta1),
              float(beta2), float(eps), float(weight_decay), int(decoupled), float(bc1), float(bc2),
-             _p(grad_scale_ptr), float(grad_scale), stream_ptr())
+             _p(grad_scale_ptr), float(grad_scale), *_ema_args(ema, n, ema_hyper, ema_one_minus_decay), *tab,
+             stream_ptr())
+
+
+def optim_step(o, p, g, m, v, p16=None, *, step=1, **kw):
+    """The element-wise update an ``OptimConfig``-like ``o`` describes, over the given flat slices: ``m`` the
+    momentum / first moment, ``v`` the second moment (unused by SGD). :func:`sgd_step` (``first=False``, see
+    :func:`reject_dampening`) for ``sgd`` / ``lars``, :func:`adam_step` at ``step`` for ``adam`` / ``adamw``;
+    LAMB is not element-wise (:func:`lamb_step`). The hyperparameters come from ``o``; ``kw`` overrides or
+    adds to them: ``lr``, ``weight_decay``, ``runs``, ``run_base``, ``grad_scale``, ``grad_scale_ptr``,
+    ``hyper`` and the three ``ema*`` keywords of the two functions."""
+    kw = {"lr": o.lr, "weight_decay": o.weight_decay, **kw}
+    if o.name in ("sgd", "lars"):
+        sgd_step(p, g, m, p16, momentum=o.momentum, dampening=getattr(o, "dampening", 0.0), nesterov=o.nesterov,
+                 first=False, **kw)
+    elif o.name in ("adam", "adamw"):
+        adam_step(p, g, m, v, p16, beta1=o.betas[0], beta2=o.betas[1], eps=o.eps, decoupled=o.name == "adamw",
+                  step=step, **kw)
+    else:
+        raise ValueError(f"optim_step: no element-wise update for optimizer {o.name!r}")
 
 
 def _chk_segments(seg_off, seg_len, adapt, n: int, what: str) -> int:
@@ -1532,15 +1522,10 @@ def lamb_step(p, g, m, v, seg_off, seg_len, adapt, norms, p16=None, *, lr, beta1
         _chk(grad_scale_ptr, torch.float32, "grad_scale_ptr", 1)
     bc1 = 1.0 - beta1 ** step
     bc2 = 1.0 - beta2 ** step
-    args = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p16), seg_off.data_ptr(), seg_len.data_ptr(),
-            adapt.data_ptr(), nseg, int(max_len), norms.data_ptr(), _p(hyper), float(lr), float(beta1), float(beta2),
-            float(eps), float(weight_decay), float(bc1), float(bc2), float(trust_min), float(trust_max),
-            _p(grad_scale_ptr), float(grad_scale))
-    if ema is not None:
-        _chk_ema(ema, n, ema_hyper)
-        C().lamb_ema(*args, ema.data_ptr(), _p(ema_hyper), float(ema_one_minus_decay), stream_ptr())
-        return
-    C().lamb(*args, stream_ptr())
+    C().lamb(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), _p(p16), seg_off.data_ptr(), seg_len.data_ptr(),
+             adapt.data_ptr(), nseg, int(max_len), norms.data_ptr(), _p(hyper), float(lr), float(beta1), float(beta2),
+             float(eps), float(weight_decay), float(bc1), float(bc2), float(trust_min), float(trust_max),
+             _p(grad_scale_ptr), float(grad_scale), *_ema_args(ema, n, ema_hyper, ema_one_minus_decay), stream_ptr())
 
 
 @_dispatch
@@ -1564,6 +1549,14 @@ def _chk_ema(ema, n: int, ema_hyper) -> None:
         _chk(ema_hyper, torch.float32, "ema_hyper", 1)
 
 
+def _ema_args(ema, n: int, ema_hyper, ema_one_minus_decay) -> Tuple[int, int, float]:
+    """The (average, omd pointer, omd) arguments of an optimizer launch, zeros without ``ema``."""
+    if ema is None:
+        return 0, 0, 0.0
+    _chk_ema(ema, n, ema_hyper)
+    return ema.data_ptr(), _p(ema_hyper), float(ema_one_minus_decay)
+
+
 @_dispatch
 def ema_update(e, p, *, one_minus_decay=0.0, hyper=None):
     """Weight EMA over two flat fp32 slices (any 4-byte aligned): ``e = fma(omd, p - e, e)`` in fp32.
@@ -1580,7 +1573,7 @@ def ema_update(e, p, *, one_minus_decay=0.0, hyper=None):
 
 
 def pack_ema_desc(pairs, device) -> torch.Tensor:
-    """Descriptor table of one :func:`ema_update_multi` launch (csrc/nn_ops.hip EmaDesc {int64 dst
+    """Descriptor table of one :func:`ema_update_multi` launch (csrc/optim_ops.hip EmaDesc {int64 dst
     address, src address, length} = 24 bytes per entry) from ``(dst, src)`` tensor pairs: flat fp32,
     contiguous, equal sizes, on ``device``. The table holds raw addresses: rebuild it if a tensor it
     names is reallocated."""

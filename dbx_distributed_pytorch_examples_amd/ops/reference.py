@@ -473,7 +473,7 @@ def ce_eval(logits, labels, stats, k, nvalid=None, loss_out=None, rank_out=None)
         rank_out.copy_(torch.where(valid, rank, torch.full_like(rank, -1)).view_as(rank_out))
 
 
-OPT_MAX_RUNS = 1024  # csrc/nn_ops.hip kOptMaxRuns (the run table lives in LDS)
+OPT_MAX_RUNS = 1024  # csrc/optim_ops.hip kOptMaxRuns (the run table lives in LDS)
 
 
 def _validate_opt_runs(starts, wds, lms, what: str = "pack_opt_runs") -> None:
@@ -605,6 +605,84 @@ def adam_step(p, g, m, v, p16=None, *, lr, beta1, beta2, eps, weight_decay, deco
         p16.copy_(p.bfloat16())
     if ema is not None:
         ema_update(ema, p, one_minus_decay=ema_one_minus_decay, hyper=ema_hyper)
+
+
+def lars_scale(p, g, seg_off, seg_len, adapt, norms, *, grad_scale, eta, weight_decay, max_len):
+    for s, (o, n, a) in enumerate(zip(seg_off.tolist(), seg_len.tolist(), adapt.tolist())):
+        w, d = p[o:o + n], g[o:o + n]
+        d.mul_(grad_scale)
+        wn, gn = w.norm(), d.norm()
+        norms[2 * s], norms[2 * s + 1] = wn * wn, gn * gn
+        if a:
+            trust = float(eta * wn / (gn + weight_decay * wn)) if (wn > 0 and gn > 0) else 1.0
+            d.add_(w, alpha=weight_decay).mul_(trust)
+
+
+def lamb_step(p, g, m, v, seg_off, seg_len, adapt, norms, p16=None, *, lr, beta1, beta2, eps, weight_decay, step,
+              trust_min=0.0, trust_max=0.0, grad_scale_ptr=None, grad_scale=1.0, hyper=None, max_len, ema=None,
+              ema_hyper=None, ema_one_minus_decay=0.0):
+    """LAMB per segment in plain fp32 torch (the kernel's formula, see kernels.lamb_step): u is left in
+    g, norms[2s], norms[2s + 1] = |w|^2, |u|^2 of segment s. Makes the wrapper's checks itself."""
+    n = p.numel()
+    for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
+        if t.dtype != torch.float32:
+            raise TypeError(f"{nm}: expected torch.float32, got {t.dtype}")
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"{nm}: expected {n} contiguous elements, got {t.numel()}")
+    if p16 is not None:
+        if p16.dtype != torch.bfloat16:
+            raise TypeError(f"p16: expected torch.bfloat16, got {p16.dtype}")
+        if p16.numel() != n:
+            raise ValueError(f"p16: expected {n} elements, got {p16.numel()}")
+    nseg = seg_off.numel()
+    for t, nm in ((seg_off, "seg_off"), (seg_len, "seg_len"), (adapt, "adapt")):
+        if t.dtype != torch.int32:
+            raise TypeError(f"{nm}: expected torch.int32, got {t.dtype}")
+        if t.numel() != nseg:
+            raise ValueError(f"{nm}: expected {nseg} elements, got {t.numel()}")
+    if norms.dtype != torch.float64:
+        raise TypeError(f"norms: expected torch.float64, got {norms.dtype}")
+    if norms.numel() != 64 * 2 * nseg:
+        raise ValueError(f"norms: expected {64 * 2 * nseg} elements, got {norms.numel()}")
+    offs, lens = seg_off.tolist(), seg_len.tolist()
+    if any(o % 4 for o in offs):
+        raise ValueError("lamb_step: every segment offset must be a multiple of 4 elements")
+    if any(o < 0 or l < 0 or o + l > n for o, l in zip(offs, lens)):
+        raise ValueError(f"lamb_step: a segment lies outside the {n}-element buffer")
+    if ema is not None:
+        _chk_ema_pair(ema, p, "lamb_step")
+    bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
+    if hyper is not None:
+        lr, bc1, bc2 = float(hyper[0]), float(hyper[1]), float(hyper[2])
+    gs = grad_scale * (float(grad_scale_ptr[0]) if grad_scale_ptr is not None else 1.0)
+    # the kernel forms 1 - b from the fp32 b (exactly): 1 - fl32(0.999) is 1.3e-5 below fl32(1 - 0.999),
+    # which v shows in full on the first step (v = (1 - b2) gg^2)
+    beta1, beta2 = (float(torch.tensor(b, dtype=torch.float32)) for b in (beta1, beta2))
+    for s, (o, ln, a) in enumerate(zip(offs, lens, adapt.tolist())):
+        w, d, mm, vv = p[o:o + ln], g[o:o + ln], m[o:o + ln], v[o:o + ln]
+        gg = d * gs
+        mm.mul_(beta1).add_(gg, alpha=1 - beta1)
+        vv.mul_(beta2).addcmul_(gg, gg, value=1 - beta2)
+        u = (mm / bc1) / (torch.sqrt(vv / bc2) + eps)
+        if a:
+            u = u + weight_decay * w
+        d.copy_(u)
+        ww, uu = (w.double() ** 2).sum(), (u.double() ** 2).sum()
+        norms[2 * s], norms[2 * s + 1] = ww, uu
+        t = 1.0
+        if a:
+            wn, un = float(torch.sqrt(ww).float()), float(torch.sqrt(uu).float())
+            if wn > 0 and un > 0:
+                t = float(torch.tensor(wn, dtype=torch.float32) / torch.tensor(un, dtype=torch.float32))
+            if trust_min > 0:
+                t = max(t, float(torch.tensor(trust_min, dtype=torch.float32)))
+            if trust_max > 0:
+                t = min(t, float(torch.tensor(trust_max, dtype=torch.float32)))
+        w.sub_(u * float(torch.tensor(lr, dtype=torch.float32) * torch.tensor(t, dtype=torch.float32)))
+        if p16 is not None:  # (like the kernel, nothing outside the segments is touched)
+            p16[o:o + ln].copy_(w.bfloat16())
+        if ema is not None and ln:
+            ema_update(ema[o:o + ln], w, one_minus_decay=ema_one_minus_decay, hyper=ema_hyper)
 
 
 def grad_accum(dst, src, *, first=False, flag=None):
@@ -1085,84 +1163,6 @@ def weight_prep(master, wbuf, desc_dev, nlayers):
 
 def cast_f32_bf16(x, y):
     y.copy_(x.bfloat16())
-
-
-def lars_scale(p, g, seg_off, seg_len, adapt, norms, *, grad_scale, eta, weight_decay, max_len):
-    for s, (o, n, a) in enumerate(zip(seg_off.tolist(), seg_len.tolist(), adapt.tolist())):
-        w, d = p[o:o + n], g[o:o + n]
-        d.mul_(grad_scale)
-        wn, gn = w.norm(), d.norm()
-        norms[2 * s], norms[2 * s + 1] = wn * wn, gn * gn
-        if a:
-            trust = float(eta * wn / (gn + weight_decay * wn)) if (wn > 0 and gn > 0) else 1.0
-            d.add_(w, alpha=weight_decay).mul_(trust)
-
-
-def lamb_step(p, g, m, v, seg_off, seg_len, adapt, norms, p16=None, *, lr, beta1, beta2, eps, weight_decay, step,
-              trust_min=0.0, trust_max=0.0, grad_scale_ptr=None, grad_scale=1.0, hyper=None, max_len, ema=None,
-              ema_hyper=None, ema_one_minus_decay=0.0):
-    """LAMB per segment in plain fp32 torch (the kernel's formula, see kernels.lamb_step): u is left in
-    g, norms[2s], norms[2s + 1] = |w|^2, |u|^2 of segment s. Makes the wrapper's checks itself."""
-    n = p.numel()
-    for t, nm in ((p, "p"), (g, "g"), (m, "m"), (v, "v")):
-        if t.dtype != torch.float32:
-            raise TypeError(f"{nm}: expected torch.float32, got {t.dtype}")
-        if t.numel() != n or not t.is_contiguous():
-            raise ValueError(f"{nm}: expected {n} contiguous elements, got {t.numel()}")
-    if p16 is not None:
-        if p16.dtype != torch.bfloat16:
-            raise TypeError(f"p16: expected torch.bfloat16, got {p16.dtype}")
-        if p16.numel() != n:
-            raise ValueError(f"p16: expected {n} elements, got {p16.numel()}")
-    nseg = seg_off.numel()
-    for t, nm in ((seg_off, "seg_off"), (seg_len, "seg_len"), (adapt, "adapt")):
-        if t.dtype != torch.int32:
-            raise TypeError(f"{nm}: expected torch.int32, got {t.dtype}")
-        if t.numel() != nseg:
-            raise ValueError(f"{nm}: expected {nseg} elements, got {t.numel()}")
-    if norms.dtype != torch.float64:
-        raise TypeError(f"norms: expected torch.float64, got {norms.dtype}")
-    if norms.numel() != 64 * 2 * nseg:
-        raise ValueError(f"norms: expected {64 * 2 * nseg} elements, got {norms.numel()}")
-    offs, lens = seg_off.tolist(), seg_len.tolist()
-    if any(o % 4 for o in offs):
-        raise ValueError("lamb_step: every segment offset must be a multiple of 4 elements")
-    if any(o < 0 or l < 0 or o + l > n for o, l in zip(offs, lens)):
-        raise ValueError(f"lamb_step: a segment lies outside the {n}-element buffer")
-    if ema is not None:
-        _chk_ema_pair(ema, p, "lamb_step")
-    bc1, bc2 = 1 - beta1 ** step, 1 - beta2 ** step
-    if hyper is not None:
-        lr, bc1, bc2 = float(hyper[0]), float(hyper[1]), float(hyper[2])
-    gs = grad_scale * (float(grad_scale_ptr[0]) if grad_scale_ptr is not None else 1.0)
-    # the kernel forms 1 - b from the fp32 b (exactly): 1 - fl32(0.999) is 1.3e-5 below fl32(1 - 0.999),
-    # which v shows in full on the first step (v = (1 - b2) gg^2)
-    beta1, beta2 = (float(torch.tensor(b, dtype=torch.float32)) for b in (beta1, beta2))
-    for s, (o, ln, a) in enumerate(zip(offs, lens, adapt.tolist())):
-        w, d, mm, vv = p[o:o + ln], g[o:o + ln], m[o:o + ln], v[o:o + ln]
-        gg = d * gs
-        mm.mul_(beta1).add_(gg, alpha=1 - beta1)
-        vv.mul_(beta2).addcmul_(gg, gg, value=1 - beta2)
-        u = (mm / bc1) / (torch.sqrt(vv / bc2) + eps)
-        if a:
-            u = u + weight_decay * w
-        d.copy_(u)
-        ww, uu = (w.double() ** 2).sum(), (u.double() ** 2).sum()
-        norms[2 * s], norms[2 * s + 1] = ww, uu
-        t = 1.0
-        if a:
-            wn, un = float(torch.sqrt(ww).float()), float(torch.sqrt(uu).float())
-            if wn > 0 and un > 0:
-                t = float(torch.tensor(wn, dtype=torch.float32) / torch.tensor(un, dtype=torch.float32))
-            if trust_min > 0:
-                t = max(t, float(torch.tensor(trust_min, dtype=torch.float32)))
-            if trust_max > 0:
-                t = min(t, float(torch.tensor(trust_max, dtype=torch.float32)))
-        w.sub_(u * float(torch.tensor(lr, dtype=torch.float32) * torch.tensor(t, dtype=torch.float32)))
-        if p16 is not None:  # (like the kernel, nothing outside the segments is touched)
-            p16[o:o + ln].copy_(w.bfloat16())
-        if ema is not None and ln:
-            ema_update(ema[o:o + ln], w, one_minus_decay=ema_one_minus_decay, hyper=ema_hyper)
 
 
 # ---- classifier head (csrc/head_ops.hip) ------------------------------------------------------------

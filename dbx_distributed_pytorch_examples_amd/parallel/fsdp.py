@@ -372,12 +372,7 @@ class ShardedDataParallel(nn.Module):
             if u.master.device != g.device:
                 g = g.to(u.master.device)
             p, m = u.master[:u.k], u.m[:u.k]
-            if o.name == "sgd":
-                K.sgd_step(p, g, m, None, lr=lr, momentum=o.momentum, dampening=getattr(o, "dampening", 0.0),
-                           weight_decay=o.weight_decay, nesterov=o.nesterov, first=False)
-            else:
-                K.adam_step(p, g, m, u.v[:u.k], None, lr=lr, beta1=o.betas[0], beta2=o.betas[1], eps=o.eps,
-                            weight_decay=o.weight_decay, decoupled=(o.name == "adamw"), step=self.step_count)
+            K.optim_step(o, p, g, m, None if u.v is None else u.v[:u.k], None, step=self.step_count, lr=lr)
             if u.dev_shard is not None and u.dev_shard is not u.master:
                 u.dev_shard[:u.k].copy_(p, non_blocking=True)
         for u in self._all():  # materialised copies are stale now (other ranks updated their shards)

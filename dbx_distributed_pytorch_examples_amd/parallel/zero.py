@@ -141,14 +141,8 @@ class ZeroShardedOptimizer:
             self._clip[2] = torch.clamp(o.grad_clip / (local.sqrt() + 1e-6), max=1.0)
             gsp = self._clip[2:3]
         lr = o.lr if lr is None else lr
-        if o.name == "sgd":
-            K.sgd_step(p, g, self.m, None, lr=lr, momentum=o.momentum, dampening=getattr(o, "dampening", 0.0),
-                       weight_decay=o.weight_decay, nesterov=o.nesterov, first=False, grad_scale_ptr=gsp,
-                       grad_scale=self.grad_scale, hyper=hyper)
-        else:
-            K.adam_step(p, g, self.m, self.v, None, lr=lr, beta1=o.betas[0], beta2=o.betas[1], eps=o.eps,
-                        weight_decay=o.weight_decay, decoupled=(o.name == "adamw"), step=self.step_count,
-                        grad_scale_ptr=gsp, grad_scale=self.grad_scale, hyper=hyper)
+        K.optim_step(o, p, g, self.m, self.v, None, step=self.step_count, lr=lr, grad_scale_ptr=gsp,
+                     grad_scale=self.grad_scale, hyper=hyper)
         if self.world == 1:
             self.master[self.lo:self.hi].copy_(p[:n_own])
             return
@@ -372,15 +366,9 @@ class SegmentedZero:
             p = self.prog.master[own:own + per]
             g = self._gpart(part)
             p16 = self.param16[own:own + per] if not self.coll else self.p16sh[so:so + per]
-            m = self.m[so:so + per]
-            if o.name == "sgd":
-                K.sgd_step(p, g, m, p16, lr=lr, momentum=o.momentum, dampening=getattr(o, "dampening", 0.0),
-                           weight_decay=o.weight_decay, nesterov=o.nesterov, first=False, grad_scale_ptr=gsp,
-                           grad_scale=gs, hyper=hyper)
-            else:
-                K.adam_step(p, g, m, self.v[so:so + per], p16, lr=lr, beta1=o.betas[0], beta2=o.betas[1], eps=o.eps,
-                            weight_decay=o.weight_decay, decoupled=(o.name == "adamw"), step=max(1, self.step_count),
-                            grad_scale_ptr=gsp, grad_scale=gs, hyper=hyper)
+            v = None if self.v is None else self.v[so:so + per]
+            K.optim_step(o, p, g, self.m[so:so + per], v, p16, step=max(1, self.step_count), lr=lr, grad_scale_ptr=gsp,
+                         grad_scale=gs, hyper=hyper)
 
     def state_dict(self):
         return {"stage": self.stage, "step": self.step_count, "rank": self.rank, "world": self.world,

@@ -113,11 +113,8 @@ def bench_kernels(n, tables, rounds, launches, out):
 
     def call(kind, tab):
         wd = dict(weight_decay=0.0, runs=tab, run_base=0) if tab is not None else dict(weight_decay=5e-5)
-        if kind == "sgd":
-            K.sgd_step(p, gr, m, None, lr=1e-3, momentum=0.9, hyper=hyper, **wd)
-        else:
-            K.adam_step(p, gr, m, v, None, lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, decoupled=True, step=1,
-                        hyper=hyper, **wd)
+        o = OptimConfig(name="sgd" if kind == "sgd" else "adamw", lr=1e-3)  # momentum 0.9, betas (0.9, 0.999), eps 1e-8
+        K.optim_step(o, p, gr, m, v, None, hyper=hyper, **wd)
 
     def window(kind, tab):
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
