@@ -1,5 +1,6 @@
 // Argument structs shared by the kernel translation units and the pybind11 bindings.
 #pragma once
+#include <stddef.h>
 typedef __bf16 bf16;
 namespace dbx {
 // BatchNorm finalize descriptor (device-resident, one per BN and direction): what bn_finalize
@@ -23,6 +24,8 @@ struct BnFin {
   int C, nshard, mode, accumulate;
   float count, eps, momentum, pad_;
 };
+// ops/kernels.py BnFin packs this by byte offset: 13 pointers, the ints at 104, the floats at 120
+static_assert(sizeof(BnFin) == 136 && offsetof(BnFin, C) == 104 && offsetof(BnFin, count) == 120, "BnFin layout");
 struct IGemmArgs {
   const bf16* x;          // A source, NHWC [N][IH][IW][IC]
   const bf16* w;          // B, [OC][KTOT] with KTOT = R*S*IC (STEM: 8*32)

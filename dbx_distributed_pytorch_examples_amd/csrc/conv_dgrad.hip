@@ -1,5 +1,6 @@
 // Data-gradient instantiations of igemm_kernel (conv_igemm_kernel.h): its own translation unit.
 #include "conv_igemm_kernel.h"
+#include "entry.h"
 
 using namespace dbx;
 

@@ -19,7 +19,7 @@
 // along pixels) alike (exhaustive check: tools/lds_banks.py). Each workgroup writes one fp32
 // partial slab of dW; wgrad_reduce sums them in a fixed order (deterministic).
 #include "common.h"
-#include "abi.h"
+#include "entry.h"
 
 namespace dbx {
 

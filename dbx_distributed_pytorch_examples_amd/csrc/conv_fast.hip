@@ -20,6 +20,7 @@
 // WM x WN = 2 x 4 (BN = 256) or 4 x 2 (BN = 128) waves. The epilogue is the shared igemm_epilogue
 // (statistics on the matrix cores, BN-backward moments, residual-gradient accumulation).
 #include "conv_igemm_kernel.h"
+#include "entry.h"
 
 namespace dbx {
 

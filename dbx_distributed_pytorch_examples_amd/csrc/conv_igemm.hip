@@ -2,6 +2,7 @@
 // The igemm_kernel template lives in conv_igemm_kernel.h; the dgrad instantiations are compiled
 // in conv_dgrad.hip (a separate translation unit, so the two compile in parallel).
 #include "conv_igemm_kernel.h"
+#include "entry.h"
 
 namespace dbx {
 
@@ -594,11 +595,6 @@ __global__ void wgrad_reduce_gather_kernel(const float* __restrict__ ws, float* 
 
 using namespace dbx;
 
-int dbx_dispatch_dgrad(int bm, int bn, const IGemmArgs& a, bool accum, int epi, int dma, hipStream_t st);  // conv_dgrad.hip
-extern "C" int dbx_conv_patch3(int mode, const IGemmArgs* args, int pro, int stats, int epi, hipStream_t st,
-                               int streamed);
-extern "C" int dbx_stem_patch(const IGemmArgs* args, int stats, hipStream_t st);
-
 template <int BM, int BN>
 static int dispatch_fwd(const IGemmArgs& a, bool pro, bool stats, int dma, hipStream_t st) {
   if (a.res) {
@@ -616,10 +612,6 @@ static int dispatch_fwd(const IGemmArgs& a, bool pro, bool stats, int dma, hipSt
   if (stats) DBX_DMA_PLAIN(launch_igemm_t, BM, BN, FWD, false, true, false, 0, false);
   DBX_DMA_PLAIN(launch_igemm_t, BM, BN, FWD, false, false, false, 0, false);
 }
-
-
-extern "C" int dbx_conv_fast(int mode, int bn, const IGemmArgs* args, int stats, int accum, int epi, hipStream_t st);
-extern "C" int dbx_conv_sweep(int mode, const IGemmArgs* args, int pro, int stats, int accum, int epi, hipStream_t st);
 
 extern "C" int dbx_conv_igemm(int mode, int bm, int bn, const IGemmArgs* args, int pro, int stats,
                               int accum, int epi, hipStream_t st, int dma) {

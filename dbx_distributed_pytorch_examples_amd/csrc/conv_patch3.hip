@@ -20,6 +20,7 @@
 // distinct 16-byte bank groups for every shift (found by exhaustive search over the gfx950 lane
 // groups; the row swizzle (x >> 1) & 7 gave 2-way conflicts on odd shifts).
 #include "conv_igemm_kernel.h"
+#include "entry.h"
 
 namespace dbx {
 

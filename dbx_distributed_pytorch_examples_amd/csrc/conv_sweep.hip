@@ -22,6 +22,7 @@
 // Measured and rejected variants: deferred epilogue stores (r6_defer/), a 4-slot ring of 32-channel
 // weight stages (r6_ring4/).
 #include "conv_igemm_kernel.h"
+#include "entry.h"
 
 namespace dbx {
 

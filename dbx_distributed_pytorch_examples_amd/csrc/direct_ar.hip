@@ -27,6 +27,7 @@
 // element it owns in the result, so a partial sum can never pass as a gradient; the error bit also
 // lands in a pinned host word that the comm watchdog polls without a device sync.
 #include "common.h"
+#include "entry.h"
 
 namespace dbx {
 

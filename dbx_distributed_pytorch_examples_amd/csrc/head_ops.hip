@@ -20,7 +20,7 @@
 // probability keep (scaled 1/keep) by a Philox-4x32-10 draw at counter (i / 4, seed_lo, seed_hi,
 // offset): the backward regenerates exactly the forward's mask from (seed, offset), no mask tensor.
 #include "common.h"
-#include "abi.h"
+#include "entry.h"
 
 namespace dbx {
 

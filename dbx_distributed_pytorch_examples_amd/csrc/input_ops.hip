@@ -25,6 +25,7 @@
 // sit inside a `#pragma clang fp contract(off)` scope (only the three TrivialAugment functions that carry it do).
 #include "common.h"
 #include "philox.h"
+#include "entry.h"
 
 namespace dbx {
 

@@ -15,6 +15,7 @@
 // Parameter layout (flat, module registration order): conv1.w [10][1][5][5], conv1.b [10],
 // conv2.w [20][10][5][5], conv2.b [20], fc1.w [50][320], fc1.b [50], fc2.w [10][50], fc2.b [10].
 #include "common.h"
+#include "entry.h"
 
 namespace dbx {
 namespace mnist {

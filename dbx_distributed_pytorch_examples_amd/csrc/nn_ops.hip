@@ -17,6 +17,7 @@
 // The optimizers over the flat fp32 master buffer (the foreach optimizer, K17) are in optim_ops.hip.
 #include "common.h"
 #include "bn_fin.h"
+#include "entry.h"
 
 namespace dbx {
 
@@ -72,7 +73,10 @@ __global__ void bn_eval_coeff_kernel(int C, const float* gamma, const float* bet
 // The same for every BatchNorm of a model in ONE launch: a device table of descriptors, grid
 // (blocks, n_bn) with blockIdx.y the entry (built as ema_kernel's table is). gamma / beta may be null
 // (0) per entry. The per-element expression is bn_eval_coeff_kernel's: bit-identical results.
-struct BnEvalDesc { long long gamma, beta, rm, rv, scale, shift; int C; float eps; };  // 56 bytes
+struct BnEvalDesc { long long gamma, beta, rm, rv, scale, shift; int C; float eps; };
+// ops/reference.py bn_eval_desc_dtype, packed by ops/kernels.py pack_bn_eval_desc
+static_assert(sizeof(BnEvalDesc) == 56 && offsetof(BnEvalDesc, C) == 48 && offsetof(BnEvalDesc, eps) == 52,
+              "BnEvalDesc layout");
 __global__ void bn_eval_coeff_multi_kernel(const BnEvalDesc* __restrict__ desc) {
   const BnEvalDesc d = desc[blockIdx.y];
   const float* gamma = reinterpret_cast<const float*>(d.gamma);
@@ -799,6 +803,7 @@ __global__ void ce_eval_kernel(const T* __restrict__ logits, const long long* __
 // Weight prep: fp32 KRSC master -> bf16 KRSC (fwd) and bf16 CRSK (dgrad) ; batched over layers
 // ----------------------------------------------------------------------------------------
 struct WDesc { long long src, fwd, tr; int K, RS, C, pad; };
+static_assert(sizeof(WDesc) == 40 && offsetof(WDesc, K) == 24, "WDesc layout (ops/kernels.py pack_wdesc)");
 // blockIdx.y = layer. Layers with a dgrad copy (K, C multiples of 64) are processed in 64x64
 // (k, c) tiles per tap through LDS so both the KRSC and the transposed CRSK stores are
 // coalesced; the others (fc) are a plain vectorised cast.

@@ -11,6 +11,7 @@
 // one __forceinline__ function below; each optimizer has one C entry point that picks the instantiation from
 // its nullable arguments.
 #include "common.h"
+#include "entry.h"
 
 namespace dbx {
 
@@ -396,6 +397,7 @@ __global__ void grad_accum_kernel(float* __restrict__ dst, const float* __restri
 // Alignment policy of grad_accum_kernel, per entry: 16 B per lane when both pointers are 16-byte
 // aligned, scalar otherwise and for the n % 4 tail.
 struct EmaDesc { long long dst, src, len; };
+static_assert(sizeof(EmaDesc) == 24 && offsetof(EmaDesc, len) == 16, "EmaDesc layout (ops/kernels.py pack_ema_desc)");
 __global__ void ema_kernel(const EmaDesc* __restrict__ desc, float* __restrict__ e, const float* __restrict__ p,
                            long long n, const float* __restrict__ omd_ptr, float omd) {
   if (desc) {

@@ -27,14 +27,7 @@
 
 #include <pybind11/stl.h>
 
-extern "C" {
-int dbx_dar_launch(float* const*, unsigned* const*, unsigned*, int*, int*, long long, int, int, int, double, hipStream_t);
-int dbx_dar_alloc(int, void**, void**, void**, void**, void**);
-int dbx_dar_free(void*, void*, void*, void*);
-int dbx_dar_max_ranks();
-int dbx_dar_launch_multi(float* const*, unsigned* const*, unsigned* const*, int* const*, long long, int, int, double,
-                         hipStream_t);
-}
+#include "entry.h"
 
 namespace py = pybind11;
 

@@ -17,7 +17,7 @@
 // transposed fragment reads, as in the wgrad kernels). One fp32 slab per workgroup; wgrad_reduce
 // sums the slabs in a fixed order (deterministic).
 #include "common.h"
-#include "abi.h"
+#include "entry.h"
 
 namespace dbx {
 

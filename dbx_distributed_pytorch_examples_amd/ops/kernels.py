@@ -9,6 +9,10 @@ calls are captured by ``torch.cuda.graph``), and never synchronises. Layout conv
 * conv weights: KRSC bf16 ``[OC, R*S*IC]`` for forward, CRSK ``[IC, R*S*OC]`` for dgrad,
   the stem as ``[64, 8*8*4]`` (7x7x3 zero-padded to 8x8x4);
 * BN statistics: fp64 ``[nshard, 2, C]`` slabs accumulated by conv epilogues (order-independent).
+
+What each ``C().<name>`` takes is the ``dbx_<name>`` declaration in ``csrc/entry.h``, argument for argument; the
+entries that fill an argument struct of ``csrc/abi.h`` (``conv_igemm``, ``conv_wgrad``, ``wgrad_patch3``,
+``conv_dwfused``, ``stem_bwd``, ``small_gemm``) are called by keyword, each argument named after its field.
 """
 from __future__ import annotations
 
@@ -25,8 +29,7 @@ from ..engine_config import EngineConfig
 _E = EngineConfig.current  # kernel-selection switches (engine_config.py; DBX_ENGINE overrides)
 
 FWD, DGRAD, STEM, FWD_PATCH, DGRAD_PATCH = 0, 1, 2, 3, 4
-# addsrc, add_sub, epi, mbits, ybn, ybn2, bsc, bsh, mean1, inv1, mean2, inv2, bstats1, bstats2
-_NO_EPI = (0, 1, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+_SPLITK = ("ksplit", "kper", "skws", "skcnt")  # conv_igemm's names for what conv_splitk returns
 MASK_NONE, MASK_OUT, MASK_Y = 0, 1, 2
 
 
@@ -73,9 +76,10 @@ NSHARD = _ref.NSHARD  # BN-statistics shards (spreads the epilogue atomics over 
 
 
 class BnFin:
-    """In-launch BatchNorm finalize descriptor (csrc/abi.h BnFin, csrc/bn_fin.h): handed to the conv
-    that accumulates a BN's statistics (``conv_fwd(fin=)`` for the forward statistics, ``BNBwdEpilogue
-    (fin1=, fin2=)`` for the backward ones), it makes the producer's last tile of every 64-channel group
+    """In-launch BatchNorm finalize descriptor (csrc/abi.h BnFin, which asserts the byte layout packed here;
+    csrc/bn_fin.h): handed to the conv that accumulates a BN's statistics (``conv_fwd(fin=)`` for the forward
+    statistics, ``BNBwdEpilogue(fin1=, fin2=)`` for the backward ones), it makes the producer's last tile of every
+    64-channel group
     compute what ``bn_finalize`` (mode 1) / ``bn_bwd_coeff`` (mode 2) would, bit for bit -- one launch
     and one graph node fewer per BN and direction. Producers that cannot (reference ops on the CPU,
     multi-launch strided dgrads, the stem) call :meth:`run` instead, so after the producer returns the
@@ -346,13 +350,14 @@ def conv_fwd(x, w16, out, *, R, S, stride, pad, stats=None, in_scale=None, in_sh
     s0, ns = fwd_taps(IW, OW, S, stride, pad)
     if nr == 0 or ns == 0:
         raise ValueError("conv_fwd: no filter tap touches the input")
-    sk = (conv_splitk(N * OH * OW, OC, bm, bn, dma, nr * ns * (IC // (32 if dma == 6 else 64)))
-          if mode == FWD else (1, 0, 0, 0))
-    C().conv_igemm(mode, bm, bn, x.data_ptr(), w16.data_ptr(), out.data_ptr(), _p(in_scale), _p(in_shift),
-                   int(relu_in), _p(stats), _nsh(stats, OC), N, IH, IW, IC, OH, OW, OC, R, S, stride, pad, 0,
-                   nr, ns, r0, s0, 1, 0, 0, 1, 0, 0, OH, OW, *_NO_EPI, 0, _p(tail_res), _p(tail_res_scale),
-                   _p(tail_res_shift), _p(tail_out), _p(tail_bits), stream_ptr(), dma, f1, 0, _fin[0], _fin[1], fi,
-                   *sk)
+    sk = (dict(zip(_SPLITK, conv_splitk(N * OH * OW, OC, bm, bn, dma, nr * ns * (IC // (32 if dma == 6 else 64)))))
+          if mode == FWD else {})
+    C().conv_igemm(mode=mode, bm=bm, bn=bn, x=x.data_ptr(), w=w16.data_ptr(), y=out.data_ptr(),
+                   in_scale=_p(in_scale), in_shift=_p(in_shift), relu_in=int(relu_in), stats=_p(stats),
+                   nshard=_nsh(stats, OC), N=N, IH=IH, IW=IW, IC=IC, OH=OH, OW=OW, OC=OC, R=R, S=S, stride=stride,
+                   pad=pad, nr=nr, ns=ns, r0=r0, s0=s0, FH=OH, FW=OW, res=_p(tail_res), res_scale=_p(tail_res_scale),
+                   res_shift=_p(tail_res_shift), tail_out=_p(tail_out), tail_bits=_p(tail_bits), st=stream_ptr(),
+                   dma=dma, fin1=f1, fin_base=_fin[0], fin_final=_fin[1], fin_in=fi, **sk)
     if fin is not None and not f1 and _fin[1]:
         fin.run()
     return out
@@ -525,9 +530,12 @@ class BNBwdEpilogue:
                              scale=self.scale, shift=self.shift, ybn2=sl(self.ybn2), mean2=self.mean2, inv2=self.inv2,
                              stats2=self.stats2, act_out=sl(self.act_out), fin1=self.fin1, fin2=self.fin2)
 
-    def args(self):
-        return (self.mode, _p(self.mbits), _p(self.ybn), _p(self.ybn2), _p(self.scale), _p(self.shift),
-                _p(self.mean1), _p(self.inv1), _p(self.mean2), _p(self.inv2), _p(self.stats1), _p(self.stats2))
+    def args(self) -> dict:
+        """The epilogue's arguments of ``conv_igemm``, by name (``a_out`` included): splatted into the call by
+        :func:`conv_dgrad`, the only caller."""
+        return dict(epi=self.mode, mbits=_p(self.mbits), ybn=_p(self.ybn), ybn2=_p(self.ybn2), bsc=_p(self.scale),
+                    bsh=_p(self.shift), mean1=_p(self.mean1), inv1=_p(self.inv1), mean2=_p(self.mean2),
+                    inv2=_p(self.inv2), bstats1=_p(self.stats1), bstats2=_p(self.stats2), a_out=_p(self.act_out))
 
 
 @_dispatch
@@ -559,7 +567,7 @@ def conv_dgrad(dy, wt16, dx, *, R, S, stride, pad, accumulate=False, tile=None, 
         if H % add_sub or W % add_sub:
             raise ValueError("addsrc subsampling must divide the output size")
         accumulate = True
-    epi = (0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0)
+    epi = {}
     nsh = NSHARD
     if epilogue is not None:
         e = epilogue
@@ -576,14 +584,12 @@ def conv_dgrad(dy, wt16, dx, *, R, S, stride, pad, accumulate=False, tile=None, 
                 raise ValueError("act_out needs the MASK_Y epilogue")
             _chk(e.act_out, torch.bfloat16, "act_out", dx.numel())
         epi = e.args()
-        act_ptr = _p(e.act_out)
         fins = (e.fin1.ptr() if e.fin1 is not None else 0, e.fin2.ptr() if e.fin2 is not None and e.stats2 is not None else 0)
         if fins[1] and not fins[0]:
             fins = (0, 0)
     else:
-        act_ptr = 0
         fins = (0, 0)
-    bwd = (0, 0, 0, 0, 0, 0)  # in_scale, in_shift, res, res_scale, res_shift, tail_out
+    bwd = {}
     if bwd_y is not None:
         if not tail_supported(K, R, S, stride, pad):
             raise ValueError("BN-backward prologue needs a 1x1 stride-1 dgrad with <= 1024 channels")
@@ -592,13 +598,13 @@ def conv_dgrad(dy, wt16, dx, *, R, S, stride, pad, accumulate=False, tile=None, 
         if dy_out is not None:
             _chk(dy_out, torch.bfloat16, "dy_out", dy.numel())
         c0 = bwd_coeff.data_ptr()
-        bwd = (c0, c0 + 8 * K, bwd_y.data_ptr(), c0 + 4 * K, 0, _p(dy_out))
+        bwd = dict(in_scale=c0, in_shift=c0 + 8 * K, res=bwd_y.data_ptr(), res_scale=c0 + 4 * K, tail_out=_p(dy_out))
     kind = (_use_patch3(tile, "dgrad") if not accumulate and bwd_y is None and (epilogue is None or epilogue.mode == MASK_Y)
             and patch3_supported(K, Cc, R, S, stride, pad, H, W) else 0)
     if kind:
-        C().conv_igemm(DGRAD_PATCH, 0, 0, dy.data_ptr(), wt16.data_ptr(), dx.data_ptr(), 0, 0, 0, 0, nsh,
-                       N, P, Q, K, H, W, Cc, R, S, stride, pad, 0, R, S, 0, 0, 1, 0, 0, 1, 0, 0, H, W,
-                       0, 1, *epi, act_ptr, 0, 0, 0, 0, 0, stream_ptr(), kind - 1, *fins, 0, 1, 0, 1, 0, 0, 0)
+        C().conv_igemm(mode=DGRAD_PATCH, bm=0, bn=0, x=dy.data_ptr(), w=wt16.data_ptr(), y=dx.data_ptr(), nshard=nsh,
+                       N=N, IH=P, IW=Q, IC=K, OH=H, OW=W, OC=Cc, R=R, S=S, stride=stride, pad=pad, nr=R, ns=S, r0=0,
+                       s0=0, FH=H, FW=W, st=stream_ptr(), dma=kind - 1, fin1=fins[0], fin2=fins[1], **epi)
         _fin_rest(epilogue, fins)
         return dx
     if isinstance(tile, str):
@@ -643,14 +649,14 @@ def conv_dgrad(dy, wt16, dx, *, R, S, stride, pad, accumulate=False, tile=None, 
             continue
         bm, bn, dma = _tile_dma(tile or pick_tile(N * ohs * ows, Cc, f"dgrad{epilogue.mode if epilogue else 0}"
                                                   + ("b" if bwd_y is not None else ""), K, R, stride))
-        sk = conv_splitk(N * ohs * ows, Cc, bm, bn, dma, nr * ns * (K // (32 if dma == 6 else 64)))
+        sk = dict(zip(_SPLITK, conv_splitk(N * ohs * ows, Cc, bm, bn, dma, nr * ns * (K // (32 if dma == 6 else 64)))))
         if dma == 8:  # the N-sweep kernel takes its grid cap in the (unused) split-K slice field
-            sk = (1, _E().sweep_dgrad_wgs, 0, 0)
-        C().conv_igemm(DGRAD, bm, bn, dy.data_ptr(), wt16.data_ptr(), dx.data_ptr(), bwd[0], bwd[1], 0, 0, nsh,
-                       N, P, Q, K, ohs, ows, Cc, R, S, stride, pad, int(accumulate),
-                       nr, ns, r0, s0, stride, dh0, dw0, stride, ph, pw, H, W,
-                       _p(addsrc), add_sub, *epi, act_ptr, bwd[2], bwd[3], bwd[4], bwd[5], 0, stream_ptr(), dma,
-                       *fins, _fin[0], _fin[1], 0, *sk)
+            sk = dict(kper=_E().sweep_dgrad_wgs)
+        C().conv_igemm(mode=DGRAD, bm=bm, bn=bn, x=dy.data_ptr(), w=wt16.data_ptr(), y=dx.data_ptr(), nshard=nsh,
+                       N=N, IH=P, IW=Q, IC=K, OH=ohs, OW=ows, OC=Cc, R=R, S=S, stride=stride, pad=pad,
+                       accum=int(accumulate), nr=nr, ns=ns, r0=r0, s0=s0, tstep=stride, dh0=dh0, dw0=dw0, osub=stride,
+                       oph=ph, opw=pw, FH=H, FW=W, addsrc=_p(addsrc), add_sub=add_sub, st=stream_ptr(), dma=dma,
+                       fin1=fins[0], fin2=fins[1], fin_base=_fin[0], fin_final=_fin[1], **epi, **bwd, **sk)
     if _fin[1]:
         _fin_rest(epilogue, fins)
     return dx
@@ -691,9 +697,9 @@ def conv_stem_fwd(x4, w16s, out, *, R=7, S=7, stride=2, pad=3, stats=None, patch
     if patch is None:
         patch = _E().stem_patch
     bm = 0 if patch and stem_patch_supported(IH, IW, OC, R, S, stride, pad) else 128  # bm 0: patch kernel
-    C().conv_igemm(STEM, bm, 64, x4.data_ptr(), w16s.data_ptr(), out.data_ptr(), 0, 0, 0, _p(stats), _nsh(stats, OC),
-                   N, IH, IW, 4, OH, OW, OC, R, S, stride, pad, 0, R, S, 0, 0, 1, 0, 0, 1, 0, 0, OH, OW,
-                   *_NO_EPI, 0, 0, 0, 0, 0, 0, stream_ptr(), 0, 0, 0, 0, 1, 0, 1, 0, 0, 0)
+    C().conv_igemm(mode=STEM, bm=bm, bn=64, x=x4.data_ptr(), w=w16s.data_ptr(), y=out.data_ptr(), stats=_p(stats),
+                   nshard=_nsh(stats, OC), N=N, IH=IH, IW=IW, IC=4, OH=OH, OW=OW, OC=OC, R=R, S=S, stride=stride,
+                   pad=pad, nr=R, ns=S, r0=0, s0=0, FH=OH, FW=OW, st=stream_ptr(), dma=0)
     return out
 
 
@@ -820,9 +826,9 @@ def conv_wgrad(dy, x, dw, ws, *, R, S, stride, pad, in_scale=None, in_shift=None
         # 3x3 patch kernel (csrc/conv_patch3.hip): one fp32 slab per persistent workgroup
         if (num_cus() + 64) * OC * R * S * IC > ws.numel():  # one slab per CU + the reduction's partials
             raise ValueError("wgrad workspace too small for the patch kernel")
-        nsl = C().wgrad_patch3(dy.data_ptr(), x.data_ptr(), ws.data_ptr(), ws.numel(), N, IH, IW, IC, OH, OW, OC, R,
-                               S, stride, pad, stream_ptr(),
-                               0)  # (honouring cu_reserve here measured slower: profiles/r5_cu_reserve/)
+        # (max_wg left at 0, all CUs: honouring cu_reserve here measured slower, profiles/r5_cu_reserve/)
+        nsl = C().wgrad_patch3(dy=dy.data_ptr(), x=x.data_ptr(), ws=ws.data_ptr(), ws_cap=ws.numel(), N=N, IH=IH, IW=IW,
+                               IC=IC, OH=OH, OW=OW, OC=OC, R=R, S=S, stride=stride, pad=pad, st=stream_ptr())
         C().wgrad_reduce(ws.data_ptr(), dw.data_ptr(), OC * KTOT, nsl, float(scale), int(accumulate), stream_ptr())
         return dw
     if isinstance(tile, str):
@@ -830,8 +836,9 @@ def conv_wgrad(dy, x, dw, ws, *, R, S, stride, pad, in_scale=None, in_shift=None
     if stem and OC == 64 and R <= 8 and S <= 8 and tile is None and _stem_wgrad_tile():
         # one 64 x 256 tile per workgroup (csrc/stem_bwd.hip, plain mode): dy read once
         _chk(dy, torch.bfloat16, "dy", N * OH * OW * 64)
-        n = C().stem_bwd(0, 0, dy.data_ptr(), 0, 0, 0, x.data_ptr(), ws.data_ptr(), ws.numel(), N, OH, OW, OC, 0, 0,
-                         0, 1, 0, IH, IW, R, S, stride, pad, 0, stream_ptr())
+        n = C().stem_bwd(y=dy.data_ptr(), x4=x.data_ptr(), ws=ws.data_ptr(), ws_cap=ws.numel(), N=N, H=OH, W=OW, C=OC,
+                         P=0, Q=0, PK=0, pstride=1, ppad=0, IH=IH, IW=IW, R=R, S=S, stride=stride, pad=pad,
+                         st=stream_ptr())
         if out_krsc is not None:  # (the image's real channels: x carries them padded to 4)
             icr = out_krsc.numel() // (OC * R * S)
             _chk(out_krsc, torch.float32, "out_krsc", OC * R * S * icr)
@@ -883,10 +890,12 @@ def conv_wgrad(dy, x, dw, ws, *, R, S, stride, pad, in_scale=None, in_shift=None
         region = defer.alloc((nsplit + (min(64, nsplit) if nsplit > 8 else 0)) * OC * KTOT)
         if region is not None:
             ws = region
-    C().conv_wgrad(STEM if stem else FWD, bm, bn, dy.data_ptr(), x.data_ptr(), ws.data_ptr(), _p(in_scale),
-                   _p(in_shift), int(relu_in), N, IH, IW, IC, OH, OW, OC, R, S, stride, pad, KTOT, nsplit, ms,
-                   stream_ptr(), int(lds_pad), int(dma), dw.data_ptr() if fuse else 0,
-                   cnt.data_ptr() if fuse and cnt is not None else 0, float(scale), int(accumulate))
+    C().conv_wgrad(mode=STEM if stem else FWD, bm=bm, bn=bn, dy=dy.data_ptr(), x=x.data_ptr(), ws=ws.data_ptr(),
+                   in_scale=_p(in_scale), in_shift=_p(in_shift), relu_in=int(relu_in), N=N, IH=IH, IW=IW, IC=IC, OH=OH,
+                   OW=OW, OC=OC, R=R, S=S, stride=stride, pad=pad, KTOT=KTOT, nsplit=nsplit, m_per_split=ms,
+                   st=stream_ptr(), lds_pad=int(lds_pad), dma=int(dma), dw=dw.data_ptr() if fuse else 0,
+                   cnt=cnt.data_ptr() if fuse and cnt is not None else 0, scale=float(scale),
+                   accumulate=int(accumulate))
     if region is not None:
         defer.add(ws, dw, OC * KTOT, nsplit, scale, accumulate)
     elif not fuse:
@@ -957,9 +966,10 @@ def conv_dwfused(g, y3, coeff, wt16, y2, scale2, shift2, mean2, invstd2, bstats2
         _chk(t, torch.float32, nm, Cc)
     if not dwfused_supported(Cc, Kc, M):
         raise ValueError(f"conv_dwfused: unsupported geometry C={Cc} K={Kc} M={M}")
-    n = C().conv_dwfused(g.data_ptr(), y3.data_ptr(), coeff.data_ptr(), wt16.data_ptr(), y2.data_ptr(),
-                         scale2.data_ptr(), shift2.data_ptr(), mean2.data_ptr(), invstd2.data_ptr(), da.data_ptr(),
-                         bstats2.data_ptr(), ws.data_ptr(), ws.numel(), M, Kc, Cc, nsh2, stream_ptr(), int(cus))
+    n = C().conv_dwfused(g=g.data_ptr(), y3=y3.data_ptr(), coeff=coeff.data_ptr(), wt=wt16.data_ptr(),
+                         y2=y2.data_ptr(), bsc=scale2.data_ptr(), bsh=shift2.data_ptr(), mean2=mean2.data_ptr(),
+                         inv2=invstd2.data_ptr(), da=da.data_ptr(), bstats=bstats2.data_ptr(), ws=ws.data_ptr(),
+                         ws_cap=ws.numel(), M=M, K=Kc, C=Cc, nshard=nsh2, st=stream_ptr(), max_cus=int(cus))
     C().wgrad_reduce(ws.data_ptr(), dw.data_ptr(), Kc * Cc, n, 1.0, 0, stream_ptr())
     return da
 
@@ -1216,9 +1226,10 @@ def stem_bwd_fused(dpool, arg, y, scale, shift, coeff, x4, dw, ws, *, K=3, strid
         raise ValueError("stem_bwd_fused: image / stem output shapes disagree")
     if not stem_bwd_supported(Cc, K, stride, R, S):
         raise ValueError("stem_bwd_fused: unsupported geometry")
-    n = C().stem_bwd(dpool.data_ptr(), arg.data_ptr(), y.data_ptr(), scale.data_ptr(), shift.data_ptr(),
-                     coeff.data_ptr(), x4.data_ptr(), ws.data_ptr(), ws.numel(), N, H, W, Cc, Pp, Q, K, stride, pad,
-                     IH, IW, R, S, conv_stride, conv_pad, 1, stream_ptr())
+    n = C().stem_bwd(dpool=dpool.data_ptr(), arg=arg.data_ptr(), y=y.data_ptr(), sc=scale.data_ptr(),
+                     sh=shift.data_ptr(), coeff=coeff.data_ptr(), x4=x4.data_ptr(), ws=ws.data_ptr(), ws_cap=ws.numel(),
+                     N=N, H=H, W=W, C=Cc, P=Pp, Q=Q, PK=K, pstride=stride, ppad=pad, IH=IH, IW=IW, R=R, S=S,
+                     stride=conv_stride, pad=conv_pad, fused=1, st=stream_ptr())
     C().wgrad_reduce(ws.data_ptr(), dw.data_ptr(), Cc * 256, n, 1.0, 0, stream_ptr())
     return dw
 
@@ -1326,9 +1337,11 @@ def small_gemm(A, B, out, *, ta=False, tb=False, M, N, K, alpha=1.0, bias=None, 
     if ws is not None:
         _chk(ws, torch.float32, "ws")
         sk = head_splitk(M, N, K, ws.numel())
-    C().small_gemm(int(ta), int(tb), int(out.dtype == torch.float32), drop, A.data_ptr(), B.data_ptr(), out.data_ptr(),
-                   _p(bf), _p(bh), M, N, K, lda, ldb, N, float(alpha), int(accumulate), int(seed) & ((1 << 64) - 1),
-                   int(off) & 0xFFFFFFFF, thr, float(inv), _p(offd), stream_ptr(), ws.data_ptr() if sk > 1 else 0, sk)
+    C().small_gemm(ta=int(ta), tb=int(tb), out_f32=int(out.dtype == torch.float32), drop=drop, A=A.data_ptr(),
+                   B=B.data_ptr(), C=out.data_ptr(), bias_f=_p(bf), bias_h=_p(bh), M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=N,
+                   alpha=float(alpha), accumulate=int(accumulate), seed=int(seed) & ((1 << 64) - 1),
+                   offset=int(off) & 0xFFFFFFFF, thresh=thr, inv_keep=float(inv), offset_dev=_p(offd), st=stream_ptr(),
+                   ws=ws.data_ptr() if sk > 1 else 0, splitk=sk)
     return out
 
 
