@@ -118,6 +118,11 @@ class DataConfig:
     mds_local: str = ""
     shuffle: bool = True
     label_smoothing: float = 0.0
+    # the training loss on the (mixed, smoothed) targets: softmax cross-entropy, or timm's binary cross-entropy on
+    # the logits ("ResNet strikes back"); validation reports softmax CE and top-k under either
+    loss: str = "ce"                   # ce | bce
+    bce_target_threshold: Optional[float] = None  # bce: targets become t > threshold ? 1 : 0 (in [0, 1); None = soft)
+    bce_sum_classes: bool = False      # bce: the sample loss is the sum over the classes, not their mean
     cutmix_alpha: float = 0.0
     # batch mixing and erasing (engine/mix.py; torchvision's ResNet-50 recipe: mixup 0.2, cutmix 1.0, erase 0.1)
     mixup_alpha: float = 0.0           # MixUp: lam ~ Beta(a, a); 0 = off
@@ -156,10 +161,37 @@ def auto_augment_options(d: DataConfig) -> Dict[str, Any]:
     return dict(auto_augment=d.auto_augment, ta_num_bins=d.ta_num_bins)
 
 
+LOSSES = ("ce", "bce")
+
+
+def validate_loss(loss: Any = "ce", bce_target_threshold: Any = None, bce_sum_classes: Any = False) -> None:
+    """ValueError for an unknown training loss, a ``bce_target_threshold`` outside [0, 1), or a ``bce_*``
+    option while the loss is not ``bce`` (refused, never ignored). Shared by the config and the trainers."""
+    if loss not in LOSSES:
+        raise ValueError(f"unknown training loss {loss!r} (known: {', '.join(LOSSES)})")
+    thr = bce_target_threshold
+    if thr is not None:
+        if isinstance(thr, bool) or not isinstance(thr, (int, float)) or not 0.0 <= float(thr) < 1.0:
+            raise ValueError(f"bce_target_threshold must be a number in [0, 1) or None, got {thr!r}")
+    if not isinstance(bce_sum_classes, bool):
+        raise ValueError(f"bce_sum_classes must be a bool, got {bce_sum_classes!r}")
+    if loss != "bce" and (thr is not None or bce_sum_classes):
+        raise ValueError(f"bce_target_threshold / bce_sum_classes need loss='bce', the loss is {loss!r}")
+
+
+def loss_options(d: DataConfig) -> Dict[str, Any]:
+    """The trainers' training-loss arguments from ``cfg.data``, validated (:func:`validate_loss`)."""
+    kw = dict(loss=d.loss, bce_target_threshold=d.bce_target_threshold, bce_sum_classes=d.bce_sum_classes)
+    validate_loss(**kw)
+    return kw
+
+
 def validate_data(d: DataConfig) -> None:
-    """ValueError for a bad batch-mixing, erasing or auto-augment setting, whichever engine would run."""
+    """ValueError for a bad batch-mixing, erasing, auto-augment or training-loss setting, whichever engine
+    would run."""
     mix_options(d)
     auto_augment_options(d)
+    loss_options(d)
 
 
 @dataclass

@@ -66,9 +66,11 @@ int dbx_pool_bn_bwd(const bf16* dpool, const unsigned char* arg, const bf16* y, 
                     int H, int W, int C, int P, int Q, int K, int stride, int pad, int apply, hipStream_t st);
 int dbx_avgpool_fwd(const bf16* x, bf16* out, int N, int HW, int C, hipStream_t st);
 int dbx_avgpool_bwd(const bf16* dout, bf16* dx, int N, int HW, int C, hipStream_t st);
+// the training loss: kind 0 = softmax cross-entropy, 1 = binary cross-entropy on the logits (target_thresh >= 0
+// binarises the targets, negative = none; sum_classes: the row loss is summed over the classes, not averaged)
 int dbx_softmax_ce(const void* logits, int is_bf16, const long long* labels, void* dlogits, float* loss_out,
                    double* stats, int B, int C, float smoothing, float gscale, const long long* labels2,
-                   const float* lam, hipStream_t st);
+                   const float* lam, hipStream_t st, int kind, float target_thresh, int sum_classes);
 int dbx_ce_eval(const void* logits, int is_bf16, const long long* labels, double* stats, int B, int C, int k,
                 const int* nvalid, float* loss_out, int* rank_out, hipStream_t st);
 int dbx_weight_prep(const float* master, bf16* wbuf, const void* desc_dev, int nlayers, hipStream_t st);  // WDesc[]

@@ -12,6 +12,8 @@
 //     the masked gradient for the residual branch) using 3 per-channel coefficients;
 //   * maxpool consumes the stem's raw conv output with BN-apply+ReLU in its prologue;
 //   * softmax-cross-entropy, label smoothing, argmax/correct-count and dlogits in one kernel;
+//   * binary cross-entropy on the logits (the other training loss): loss, argmax and dlogits from one pass
+//     over the row (bce_logits);
 //   * evaluation: loss + label rank (top-1 / top-k counts) in one kernel without a gradient (ce_eval),
 //     every BatchNorm's eval coefficients in one table-driven launch (bn_eval_coeff_multi).
 // The optimizers over the flat fp32 master buffer (the foreach optimizer, K17) are in optim_ops.hip.
@@ -800,6 +802,73 @@ __global__ void ce_eval_kernel(const T* __restrict__ logits, const long long* __
 }
 
 // ----------------------------------------------------------------------------------------
+// Binary cross-entropy on the logits (timm's BinaryCrossEntropy on MixUp / CutMix soft targets) fused
+// with dlogits and the argmax-correct count. One wave per row, four rows per block, ONE pass over the
+// row: no row maximum and no log-sum-exp are needed, so loss, argmax and gradient come from the same
+// load of each element (scalar loads: rows of an arbitrary C are not 16-byte aligned).
+//   t_c  = softmax_ce_kernel's target, then (thresh >= 0) t_c = t_c > thresh ? 1 : 0
+//   l_c  = max(x, 0) - x t_c + log1p(exp(-|x|))      loss = sum_c l_c / D,  D = sum_classes ? 1 : C
+//   dlogits = (sigmoid(x) - t_c) * gscale / (B D)    sigmoid from the same exp(-|x|)
+// A label outside [0, C) matches no column: it is never used as an index, gives no positive class and
+// the row counts as incorrect. stats[0] += loss, stats[1] += correct (fp64; the block's rows are summed
+// in LDS first, one atomic per statistic and block).
+// ----------------------------------------------------------------------------------------
+template <typename T>
+__global__ void bce_logits_kernel(const T* __restrict__ logits, const long long* __restrict__ labels,
+                                  T* __restrict__ dlogits, float* __restrict__ loss_out, double* stats, int B, int C,
+                                  float smoothing, float gscale, const long long* __restrict__ labels2,
+                                  const float* __restrict__ lam_ptr, float thresh, int sum_classes) {
+  const int wid = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wid;
+  __shared__ float s_loss[4];
+  __shared__ int s_ok[4];
+  float loss = 0.f;
+  int ok = 0;
+  if (row < B) {  // (wave-uniform)
+    const long long lab = labels[row];
+    const long long lab2 = labels2 ? labels2[row] : lab;
+    const float lam = labels2 ? lam_ptr[0] : 1.f;
+    const int l1 = (lab >= 0 && lab < (long long)C) ? (int)lab : -1;  // -1 matches no column
+    const int l2 = (lab2 >= 0 && lab2 < (long long)C) ? (int)lab2 : -1;
+    const float D = sum_classes ? 1.f : (float)C;
+    const float inv = gscale / ((float)B * D);
+    const T* x = logits + (size_t)row * C;
+    T* dx = dlogits ? dlogits + (size_t)row * C : nullptr;
+    float mx = -INFINITY, acc = 0.f;
+    int amx = 0;
+    for (int c = lane; c < C; c += 64) {
+      const float v = (float)x[c];
+      if (v > mx) { mx = v; amx = c; }
+      float t = (1.f - smoothing) * ((c == l1 ? lam : 0.f) + (c == l2 ? 1.f - lam : 0.f)) + smoothing / C;
+      if (thresh >= 0.f) t = t > thresh ? 1.f : 0.f;
+      const float e = expf(-fabsf(v));
+      acc += fmaxf(v, 0.f) - v * t + log1pf(e);
+      if (dx) {
+        const float r = 1.f / (1.f + e);
+        dx[c] = (T)(((v >= 0.f ? r : e * r) - t) * inv);
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {  // argmax-aware max: the lowest index wins among equal values
+      const float om = __shfl_xor(mx, o, 64);
+      const int oa = __shfl_xor(amx, o, 64);
+      if (om > mx || (om == mx && oa < amx)) { mx = om; amx = oa; }
+    }
+    loss = wave_sum(acc) / D;
+    ok = (amx == l1) ? 1 : 0;
+    if (lane == 0 && loss_out) loss_out[row] = loss;
+  }
+  if (!stats) return;  // (uniform over the block)
+  if (lane == 0) { s_loss[wid] = loss; s_ok[wid] = ok; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    double v = 0.0;
+    for (int w = 0; w < 4; ++w) v += threadIdx.x == 0 ? (double)s_loss[w] : (double)s_ok[w];
+    if (v != 0.0) atomicAdd(stats + threadIdx.x, v);  // (true for NaN too: a NaN loss reaches the sum)
+  }
+}
+
+// ----------------------------------------------------------------------------------------
 // Weight prep: fp32 KRSC master -> bf16 KRSC (fwd) and bf16 CRSK (dgrad) ; batched over layers
 // ----------------------------------------------------------------------------------------
 struct WDesc { long long src, fwd, tr; int K, RS, C, pad; };
@@ -1033,7 +1102,21 @@ extern "C" int dbx_avgpool_bwd(const bf16* dout, bf16* dx, int N, int HW, int C,
 }
 extern "C" int dbx_softmax_ce(const void* logits, int is_bf16, const long long* labels, void* dlogits, float* loss_out,
                               double* stats, int B, int C, float smoothing, float gscale, const long long* labels2,
-                              const float* lam, hipStream_t st) {
+                              const float* lam, hipStream_t st, int kind, float target_thresh, int sum_classes) {
+  if (kind == 1) {  // binary cross-entropy: one wave per row
+    if (B <= 0) return 0;
+    if (!logits || !labels || C < 1 || (labels2 && !lam)) return -1;
+    const dim3 grid((B + 3) / 4);
+    if (is_bf16)
+      hipLaunchKernelGGL(bce_logits_kernel<bf16>, grid, dim3(256), 0, st, (const bf16*)logits, labels, (bf16*)dlogits,
+                         loss_out, stats, B, C, smoothing, gscale, labels2, lam, target_thresh, sum_classes);
+    else
+      hipLaunchKernelGGL(bce_logits_kernel<float>, grid, dim3(256), 0, st, (const float*)logits, labels,
+                         (float*)dlogits, loss_out, stats, B, C, smoothing, gscale, labels2, lam, target_thresh,
+                         sum_classes);
+    RET_LAST;
+  }
+  if (kind != 0) return -1;
   if (is_bf16)
     hipLaunchKernelGGL(softmax_ce_kernel<bf16>, dim3(B), dim3(256), 0, st, (const bf16*)logits, labels, (bf16*)dlogits,
                        loss_out, stats, B, C, smoothing, gscale, labels2, lam);

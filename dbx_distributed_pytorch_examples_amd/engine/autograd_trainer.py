@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from ..config import distinct_param_groups, has_param_groups, resolve_param_groups
+from ..config import distinct_param_groups, has_param_groups, resolve_param_groups, validate_loss
 from ..parallel.ddp import DistributedDataParallel, flat_view, unwrap
 
 
@@ -217,6 +217,20 @@ def soft_cross_entropy(logits: torch.Tensor, target: torch.Tensor, smoothing: fl
     return -(target * F.log_softmax(logits.float(), 1)).sum(1).mean()
 
 
+def bce_loss(logits: torch.Tensor, labels: Optional[torch.Tensor], smoothing: float = 0.0,
+             target_threshold: Optional[float] = None, sum_classes: bool = False,
+             target: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The autograd engines' binary cross-entropy: ``F.binary_cross_entropy_with_logits`` on the targets of
+    ``reference.bce_logits`` (its definition) -- from ``labels``, or from mixed one-hot rows ``target``."""
+    from ..ops import reference as R
+    logits = logits.float()
+    if target is not None:
+        t = R.bce_soft_targets(target.float(), smoothing, target_threshold)
+    else:
+        t = R.bce_targets(labels, logits.shape[1], smoothing, target_threshold=target_threshold)
+    return R.bce_with_logits_loss(logits, t, sum_classes)
+
+
 class AutogradTrainer:
     def __init__(self, model: nn.Module, device: torch.device, optim, label_smoothing: float = 0.0,
                  bucket_cap_mb: float = 64.0, channels_last: bool = True, zero_stage: int = 0,
@@ -224,7 +238,8 @@ class AutogradTrainer:
                  offload_optimizer: bool = False, offload_param: bool = False, bf16: bool = True,
                  stage3: Optional[dict] = None, mixup_alpha: float = 0.0, mix_prob: float = 1.0,
                  mix_switch_prob: float = 0.5, erase_prob: float = 0.0, erase_mode: str = "const",
-                 erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3), auto_augment=None):
+                 erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3), auto_augment=None, loss: str = "ce",
+                 bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False):
         if auto_augment is not None:  # refused, never ignored
             raise ValueError(f"auto_augment={auto_augment!r} runs in the native step's input kernels (NativeTrainer); "
                              f"the autograd engine has no such stage -- put data.transforms.TrivialAugmentWide in the "
@@ -232,6 +247,13 @@ class AutogradTrainer:
         from .mix import validate_mix
         validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, erase_mode, erase_scale,
                      erase_ratio)
+        validate_loss(loss, bce_target_threshold, bce_sum_classes)
+        m = unwrap(model)
+        if loss == "bce" and (callable(getattr(m, "loss", None)) or getattr(m, "outputs_log_probs", False)
+                              or isinstance(m, _log_prob_types())):  # refused, never ignored
+            raise ValueError(f"loss='bce' needs a model that returns logits and leaves the loss to the trainer; "
+                             f"{type(m).__name__} brings its own loss or returns log-probabilities")
+        self.loss, self.bce_target_threshold, self.bce_sum_classes = loss, bce_target_threshold, bool(bce_sum_classes)
         self.dev = device
         self.bf16 = bool(bf16) and device.type == "cuda"  # autocast bf16 (DeepSpeed bf16.enabled)
         self.model = model.to(device)
@@ -300,6 +322,8 @@ class AutogradTrainer:
 
     def _loss(self, out, x, y, target=None):
         m = unwrap(self.model)
+        if self.loss == "bce":
+            return bce_loss(out, y, self.smoothing, self.bce_target_threshold, self.bce_sum_classes, target=target)
         if hasattr(m, "loss") and callable(m.loss) and target is None:
             return m.loss(out, (x, y), label_smoothing=self.smoothing) if "label_smoothing" in m.loss.__code__.co_varnames \
                 else m.loss(out, (x, y))

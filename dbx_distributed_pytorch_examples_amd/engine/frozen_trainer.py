@@ -38,8 +38,8 @@ from ..config import OptimizerConfig
 from ..models.wrappers import FrozenBackboneClassifier
 from ..parallel.ddp import DistributedDataParallel
 from ..utils import debug as _debug
-from ..config import reject_param_groups
-from .autograd_trainer import build_torch_optimizer
+from ..config import reject_param_groups, validate_loss
+from .autograd_trainer import bce_loss, build_torch_optimizer
 from .hyper import DeviceHyper
 from .program import ResNetProgram, release_dead_graphs
 from ..engine_config import EngineConfig
@@ -60,9 +60,12 @@ class NativeHead:
     The module's Parameter objects are re-pointed at the head's flat fp32 master (``.data``)."""
 
     def __init__(self, head: nn.Module, batch: int, device: torch.device, optim: OptimizerConfig,
-                 label_smoothing: float = 0.0, seed: int = 0):
+                 label_smoothing: float = 0.0, seed: int = 0, loss: str = "ce",
+                 bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False):
         from ..ops import kernels as K
         self.K = K
+        validate_loss(loss, bce_target_threshold, bce_sum_classes)
+        self.loss, self.bce_target_threshold, self.bce_sum_classes = loss, bce_target_threshold, bool(bce_sum_classes)
         K.reject_dampening(optim)
         lins = [m for m in head.modules() if isinstance(m, nn.Linear)]
         if len(lins) != 1 or any(not isinstance(m, (nn.Linear, nn.Dropout, nn.Sequential, nn.Identity))
@@ -118,7 +121,11 @@ class NativeHead:
         K, n = self.K, feats.shape[0]
         lg, dl = self.logits[:n], self.dlogits[:n]
         K.small_gemm(feats, self.w16, lg, M=n, N=self.C, K=self.F, bias=self.b16, dropout=self._drop("A"))
-        K.softmax_ce(lg, labels, dl, None, metrics, smoothing=self.smoothing)
+        if self.loss == "bce":
+            K.bce_logits(lg, labels, dl, None, metrics, smoothing=self.smoothing,
+                         target_threshold=self.bce_target_threshold, sum_classes=self.bce_sum_classes)
+        else:
+            K.softmax_ce(lg, labels, dl, None, metrics, smoothing=self.smoothing)
         K.small_gemm(dl, feats, self.gW, ta=True, tb=True, M=self.C, N=self.F, K=n, dropout=self._drop("B"))
         K.colsum(dl, self.gb)
 
@@ -150,10 +157,13 @@ class FrozenFeatureTrainer:
     def __init__(self, model: FrozenBackboneClassifier, batch: int, image_hw: Tuple[int, int], device: torch.device,
                  optim: OptimizerConfig, label_smoothing: float = 0.0, src_hw=None, mean=None, std=None,
                  bucket_cap_mb: float = 64.0, allreduce_dtype=torch.float32, use_graphs: bool = True,
-                 auto_augment=None):
+                 auto_augment=None, loss: str = "ce", bce_target_threshold: Optional[float] = None,
+                 bce_sum_classes: bool = False):
         if auto_augment is not None:  # refused, never ignored
             raise ValueError(f"auto_augment={auto_augment!r} needs the native training step (NativeTrainer); the "
                              f"frozen-backbone trainer runs its backbone in evaluation mode, which never augments")
+        validate_loss(loss, bce_target_threshold, bce_sum_classes)
+        self.loss, self.bce_target_threshold, self.bce_sum_classes = loss, bce_target_threshold, bool(bce_sum_classes)
         self.full_model = model
         self.dev = device
         self.prog = ResNetProgram(_backbone_proxy(model), batch, image_hw, device, src_hw=src_hw, mean=mean, std=std)
@@ -166,7 +176,8 @@ class FrozenFeatureTrainer:
         eng = EngineConfig.current()
         if eng.frozen_native_head and optim.name in ("sgd", "adam", "adamw"):
             try:
-                self.nhead = NativeHead(self.head, batch, device, optim, label_smoothing)
+                self.nhead = NativeHead(self.head, batch, device, optim, label_smoothing, loss=loss,
+                                        bce_target_threshold=bce_target_threshold, bce_sum_classes=bce_sum_classes)
             except TypeError:
                 self.nhead = None  # an unsupported head module: the autograd head below
         if self.nhead is not None:
@@ -322,7 +333,10 @@ class FrozenFeatureTrainer:
         feats = feats.float()
         self.head.train()
         logits = self.ddp(feats)
-        loss = F.cross_entropy(logits, labels, label_smoothing=self.smoothing)
+        if self.loss == "bce":
+            loss = bce_loss(logits, labels, self.smoothing, self.bce_target_threshold, self.bce_sum_classes)
+        else:
+            loss = F.cross_entropy(logits, labels, label_smoothing=self.smoothing)
         self.opt.zero_grad(set_to_none=False)
         loss.backward()
         self.ddp.finish_gradient_sync()

@@ -30,7 +30,7 @@ import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from ..config import distinct_param_groups, has_param_groups, resolve_param_groups
+from ..config import distinct_param_groups, has_param_groups, resolve_param_groups, validate_loss
 from ..engine_config import EngineConfig
 from ..ops import kernels as K
 from ..parallel.dist import host_sync_for_gloo
@@ -82,7 +82,9 @@ class NativeTrainer:
                  ema_warmup: bool = False, mixup_alpha: float = 0.0, mix_prob: float = 1.0,
                  mix_switch_prob: float = 0.5, erase_prob: float = 0.0, erase_mode: str = "const",
                  erase_scale: Tuple[float, float] = (0.02, 1 / 3), erase_ratio: Tuple[float, float] = (0.3, 3.3),
-                 auto_augment: Optional[str] = None, ta_num_bins: int = 31):
+                 auto_augment: Optional[str] = None, ta_num_bins: int = 31, loss: str = "ce",
+                 bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False):
+        validate_loss(loss, bce_target_threshold, bce_sum_classes)
         validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, erase_mode, erase_scale,
                      erase_ratio)
         validate_auto_augment(auto_augment, ta_num_bins)
@@ -120,6 +122,11 @@ class NativeTrainer:
         self.prog.build_backward()
         self.opt = optim
         self.smoothing = label_smoothing
+        # the training loss: softmax CE, or binary CE on the same mixed / smoothed targets (K.bce_logits); the
+        # program's forward launches one or the other, nothing else in the step sees the choice
+        self.loss, self.bce_target_threshold, self.bce_sum_classes = loss, bce_target_threshold, bool(bce_sum_classes)
+        self.prog.loss_kind = loss
+        self.prog.bce_target_threshold, self.prog.bce_sum_classes = bce_target_threshold, bool(bce_sum_classes)
         # CutMix (Composer's CutMix(alpha), `03_composer/01_cifar_composer_resnet.ipynb:430`): per step a
         # batch permutation and one box are sampled here (host, tiny) and applied on the device by the
         # augment kernel (paste) and the CE kernel (mixed soft targets) inside the captured step
@@ -706,6 +713,12 @@ class NativeTrainer:
         self._mix_host = host  # keep the pinned sources alive until the copies ran
         for dst, src in host:
             dst.copy_(src, non_blocking=True)
+
+    def loss_summary(self) -> dict:
+        """The training-loss settings, for logging."""
+        return {"loss": self.loss, "label_smoothing": self.smoothing,
+                "bce_target_threshold": self.bce_target_threshold, "bce_sum_classes": self.bce_sum_classes,
+                "kernel": "bce_logits" if self.loss == "bce" else "softmax_ce"}
 
     def mix_summary(self) -> dict:
         """The batch-mixing settings, for logging."""

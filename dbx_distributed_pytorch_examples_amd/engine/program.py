@@ -654,6 +654,8 @@ class ResNetProgram:
         # augment kernel (box paste) and the CE kernel (mixed soft targets)
         self.cutmix = False
         self.mix_perm = self.mix_box = self.mix_lam = self.labels2 = None
+        # the training loss (NativeTrainer sets it): "ce" = K.softmax_ce, "bce" = K.bce_logits on the same targets
+        self.loss_kind, self.bce_target_threshold, self.bce_sum_classes = "ce", None, False
         # MixUp / random erasing (enable_mix): the blend weight, the per-sample erase boxes and the
         # Philox offset of the "pixel" erase noise, consumed by the mixing form of the augment kernel
         self.mix_blend = self.erase_box = self.erase_off = self._erase_ctr = self.mix_arena = None
@@ -950,6 +952,12 @@ class ResNetProgram:
         if not loss:
             return self.logits
         mix = self.cutmix and self.training
+        if self.loss_kind == "bce" and self.training:  # (an evaluation forward keeps softmax CE)
+            K.bce_logits(self.logits, self.labels, self.dlogits if compute_grad else None, None,
+                         self.metrics if metrics else None, smoothing=smoothing, grad_scale=grad_scale,
+                         labels2=self.labels2 if mix else None, lam=self.mix_lam if mix else None,
+                         target_threshold=self.bce_target_threshold, sum_classes=self.bce_sum_classes)
+            return self.logits
         K.softmax_ce(self.logits, self.labels, self.dlogits if compute_grad else None, None,
                      self.metrics if metrics else None, smoothing=smoothing, grad_scale=grad_scale,
                      labels2=self.labels2 if mix else None, lam=self.mix_lam if mix else None)

@@ -1271,7 +1271,24 @@ def softmax_ce(logits, labels, dlogits=None, loss_out=None, stats=None, smoothin
         _chk(lam, torch.float32, "lam", 1)
     C().softmax_ce(logits.data_ptr(), int(logits.dtype == torch.bfloat16), labels.data_ptr(), _p(dlogits),
                    _p(loss_out), _p(stats), B, Cc, float(smoothing), float(grad_scale), _p(labels2), _p(lam),
-                   stream_ptr())
+                   stream_ptr(), 0, -1.0, 0)
+
+
+@_dispatch
+def bce_logits(logits, labels, dlogits=None, loss_out=None, stats=None, smoothing=0.0, grad_scale=1.0,
+               labels2=None, lam=None, target_threshold=None, sum_classes=False):
+    """Binary cross-entropy on the logits (timm's ``BinaryCrossEntropy`` on :func:`softmax_ce`'s soft
+    targets) with dlogits, per-row loss and the device-side loss-sum / correct counters, from one pass over
+    each row. ``target_threshold`` binarises the smoothed, mixed targets (``t > thr ? 1 : 0``);
+    ``sum_classes``: the row loss is the sum over the classes, not their mean (``dlogits`` follows). A label
+    outside [0, C) is never used as an index: no positive class from it, the row counts as incorrect. See
+    ``reference.bce_logits``."""
+    B, Cc, thr = _ref.check_bce_logits(logits, labels, dlogits, loss_out, stats, smoothing, grad_scale, labels2, lam,
+                                       target_threshold, sum_classes)
+    _chk(logits, logits.dtype, "logits")
+    C().softmax_ce(logits.data_ptr(), int(logits.dtype == torch.bfloat16), labels.data_ptr(), _p(dlogits),
+                   _p(loss_out), _p(stats), B, Cc, float(smoothing), float(grad_scale), _p(labels2), _p(lam),
+                   stream_ptr(), 1, thr, int(bool(sum_classes)))
 
 
 @_dispatch

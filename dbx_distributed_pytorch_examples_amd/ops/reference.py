@@ -422,6 +422,91 @@ def softmax_ce(logits, labels, dlogits=None, loss_out=None, stats=None, smoothin
         dlogits.copy_(((p - t) * grad_scale / B).to(dlogits.dtype))
 
 
+def check_bce_logits(logits, labels, dlogits=None, loss_out=None, stats=None, smoothing=0.0, grad_scale=1.0,
+                     labels2=None, lam=None, target_threshold=None, sum_classes=False):
+    """Host-side argument checks of :func:`bce_logits`, shared with the kernel front-end; returns
+    (B, C, threshold as the kernel takes it: negative = none)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 2 or logits.dtype not in (torch.float32, torch.bfloat16) \
+            or not logits.is_contiguous():
+        raise TypeError("bce_logits: logits must be a contiguous [B, C] fp32 / bf16 matrix")
+    B, C = logits.shape
+    if C < 1:
+        raise ValueError("bce_logits: logits need at least one class")
+    if (labels2 is None) != (lam is None):
+        raise ValueError("bce_logits: labels2 and lam come together")
+    for t, dt, n, nm in ((labels, torch.int64, B, "labels"), (dlogits, logits.dtype, B * C, "dlogits"),
+                         (loss_out, torch.float32, B, "loss_out"), (stats, torch.float64, 2, "stats"),
+                         (labels2, torch.int64, B, "labels2"), (lam, torch.float32, 1, "lam")):
+        if t is None and nm != "labels":
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise TypeError(f"bce_logits: {nm}: expected a {dt} tensor, got {getattr(t, 'dtype', type(t))}")
+        if t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"bce_logits: {nm}: expected {n} contiguous elements, got shape {tuple(t.shape)}")
+        if t.device != logits.device:
+            raise ValueError(f"bce_logits: {nm} is on {t.device}, logits on {logits.device}")
+    if not 0.0 <= float(smoothing) < 1.0:
+        raise ValueError(f"bce_logits: smoothing must be in [0, 1), got {smoothing}")
+    if not math.isfinite(float(grad_scale)):
+        raise ValueError(f"bce_logits: grad_scale must be finite, got {grad_scale}")
+    if target_threshold is not None and not 0.0 <= float(target_threshold) < 1.0:
+        raise ValueError(f"bce_logits: target_threshold must be in [0, 1) or None, got {target_threshold}")
+    return B, C, -1.0 if target_threshold is None else float(target_threshold)
+
+
+def bce_soft_targets(mixed, smoothing=0.0, target_threshold=None):
+    """The BCE targets from mixed one-hot rows ``mixed`` [B, C] (``lam onehot(l) + (1 - lam) onehot(l2)``):
+    label smoothing on top, ``(1 - s) mixed + s / C``, then timm's ``target_threshold``: ``t > thr ? 1 : 0``."""
+    t = (1 - smoothing) * mixed + smoothing / mixed.shape[1]
+    if target_threshold is not None:
+        t = (t > target_threshold).to(t.dtype)
+    return t
+
+
+def bce_targets(labels, C, smoothing=0.0, labels2=None, lam=None, target_threshold=None, dtype=torch.float32):
+    """:func:`bce_soft_targets` of the labels [B] (``labels2`` [B] + ``lam`` [1] device tensor: the MixUp / CutMix
+    pair, read on the device). A label outside [0, C) matches no column: no positive class from it."""
+    idx = torch.arange(C, device=labels.device)[None, :]
+    mixed = (idx == labels[:, None]).to(dtype)
+    if labels2 is not None:
+        lm = lam.reshape(-1)[0].to(dtype)
+        mixed = mixed * lm + (idx == labels2[:, None]).to(dtype) * (1 - lm)
+    return bce_soft_targets(mixed, smoothing, target_threshold)
+
+
+def bce_with_logits_loss(logits, targets, sum_classes=False):
+    """The scalar training loss of the autograd engines on targets from :func:`bce_soft_targets`: timm's
+    ``loss.sum(-1).mean()`` (``sum_classes``) or ``loss.mean()``."""
+    loss = F.binary_cross_entropy_with_logits(logits.float(), targets.to(torch.float32), reduction="none")
+    return loss.sum(-1).mean() if sum_classes else loss.mean()
+
+
+def bce_logits(logits, labels, dlogits=None, loss_out=None, stats=None, smoothing=0.0, grad_scale=1.0,
+               labels2=None, lam=None, target_threshold=None, sum_classes=False):
+    """Binary cross-entropy on the logits with dlogits, on any device and without a host sync. Per row, in
+    fp32: ``t`` = :func:`bce_targets`, ``l_c = max(x, 0) - x t + log1p(exp(-|x|))``, ``loss = sum_c l_c / D``
+    with ``D = 1`` (``sum_classes``) or C, ``dlogits = (sigmoid(x) - t) grad_scale / (B D)``;
+    ``stats`` (fp64 [2], accumulated) ``+= [sum of the row losses, rows whose argmax is the label]`` (the
+    lowest index wins among equal logits; a label outside [0, C) is never correct)."""
+    B, C, _ = check_bce_logits(logits, labels, dlogits, loss_out, stats, smoothing, grad_scale, labels2, lam,
+                               target_threshold, sum_classes)
+    x = logits.float()
+    t = bce_targets(labels, C, smoothing, labels2, lam, target_threshold)
+    e = torch.exp(-x.abs())
+    D = 1 if sum_classes else C
+    loss = (x.clamp(min=0) - x * t + torch.log1p(e)).sum(1) / D
+    if loss_out is not None:
+        loss_out.copy_(loss.view_as(loss_out))
+    if stats is not None:
+        idx = torch.arange(C, device=x.device)[None, :].expand(B, C)
+        amax = torch.where(x == x.max(1, keepdim=True).values, idx, torch.full_like(idx, C)).min(1).values
+        stats += torch.stack([loss.double().sum(), ((amax == labels) & (amax < C)).sum().double()])
+    if dlogits is not None:
+        r = 1 / (1 + e)
+        sig = torch.where(x >= 0, r, e * r)
+        dlogits.copy_(((sig - t) * (grad_scale / (B * D))).to(dlogits.dtype).view_as(dlogits))
+
+
 def check_ce_eval(logits, labels, stats, k, nvalid=None, loss_out=None, rank_out=None):
     """Host-side argument checks of :func:`ce_eval`, shared with the kernel front-end; returns (B, C)."""
     if logits.dim() != 2 or logits.dtype not in (torch.float32, torch.bfloat16) or not logits.is_contiguous():

@@ -35,7 +35,7 @@ import numpy as np
 import torch
 from torch.utils.data import DataLoader, Dataset
 
-from ..config import (TrainConfig, auto_augment_options, from_deepspeed, has_param_groups, mix_options,
+from ..config import (TrainConfig, auto_augment_options, from_deepspeed, has_param_groups, loss_options, mix_options,
                       mixes_batches, parse_duration, to_dict, validate_data)
 from ..models import build_model
 from ..parallel import dist as ddist
@@ -134,7 +134,8 @@ class _Native:
             from ..engine.frozen_trainer import FrozenFeatureTrainer
             self.tr = FrozenFeatureTrainer(model, cfg.batch_size, (s, s), dev, o,
                                            label_smoothing=cfg.data.label_smoothing, src_hw=(h, w), mean=mean,
-                                           std=std, bucket_cap_mb=cfg.bucket_cap_mb, allreduce_dtype=ar)
+                                           std=std, bucket_cap_mb=cfg.bucket_cap_mb, allreduce_dtype=ar,
+                                           **loss_options(cfg.data))
         else:
             self.tr = NativeTrainer(model, cfg.batch_size, (s, s), dev,
                                     optim=OptimConfig(o.name, o.lr, o.momentum, 0.0, o.nesterov, o.weight_decay,
@@ -149,7 +150,7 @@ class _Native:
                                     src_hw=(h, w), mean=mean, std=std, zero_stage=cfg.zero.stage,
                                     seed=cfg.seed, grad_accum=cfg.grad_accum, ema_decay=cfg.ema_decay,
                                     ema_warmup=cfg.ema_warmup, **mix_options(cfg.data),
-                                    **auto_augment_options(cfg.data))
+                                    **auto_augment_options(cfg.data), **loss_options(cfg.data))
         self.ema_eval = bool(cfg.ema_eval)
         self.eval_topk, self.eval_graph = _eval_topk(cfg), bool(cfg.eval_graph)
         if not cfg.data.augment:
@@ -245,7 +246,7 @@ class _Autograd:
         from ..engine.autograd_trainer import AutogradTrainer
         self.tr = AutogradTrainer(model, dev, cfg.optim, label_smoothing=cfg.data.label_smoothing,
                                   bucket_cap_mb=cfg.bucket_cap_mb, zero_stage=cfg.zero.stage,
-                                  grad_accum=cfg.grad_accum, **mix_options(cfg.data),
+                                  grad_accum=cfg.grad_accum, **mix_options(cfg.data), **loss_options(cfg.data),
                                   offload_optimizer=cfg.zero.offload_optimizer, offload_param=cfg.zero.offload_param,
                                   bf16=cfg.precision == "bf16", stage3=_stage3_kw(cfg.zero),
                                   allreduce_dtype=torch.bfloat16 if cfg.allreduce_dtype == "bf16" else torch.float32)
@@ -449,6 +450,10 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
         if mixes_batches(cfg.data) or cfg.data.auto_augment is not None:
             s = runner.tr.mix_summary() if hasattr(runner.tr, "mix_summary") else mix_options(cfg.data)
             _log("[train] batch mixing: " + " ".join(f"{k}={v}" for k, v in s.items()))
+        if cfg.data.loss != "ce":
+            s = runner.tr.loss_summary() if hasattr(runner.tr, "loss_summary") else loss_options(cfg.data)
+            _log("[train] training loss: " + " ".join(f"{k}={v}" for k, v in s.items())
+                 + " (validation reports softmax cross-entropy)")
         if cfg.grad_accum > 1 and cfg.checkpoint_dir and cfg.checkpoint_every and spe % cfg.grad_accum != 0:
             # (one iteration is one micro-batch; a checkpoint carries no accumulator)
             _log(f"[train] warning: steps/epoch={spe} is no multiple of grad_accum={cfg.grad_accum}: a run resumed "
