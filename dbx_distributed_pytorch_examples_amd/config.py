@@ -134,8 +134,13 @@ class DataConfig:
     erase_ratio: Tuple[float, float] = (0.3, 3.3)      # rectangle height / width (log-uniform)
     # TrivialAugmentWide in the native input kernels (torchvision's --auto-augment ta_wide): one of fourteen
     # uint8-space operations per training image, at one of ta_num_bins strengths. Native engine only.
-    auto_augment: Optional[str] = None  # None | "ta_wide"
+    # "ra": RandAugment (torchvision's --auto-augment ra; timm's A1-A3 recipes), ra_num_ops operations in sequence at
+    # bin ra_magnitude of ta_num_bins. "aa_imagenet": AutoAugment's ImageNet policy (two operations on ten bins;
+    # ta_num_bins is ignored for it). The ra_* options need auto_augment: ra.
+    auto_augment: Optional[str] = None  # None | "ta_wide" | "ra" | "aa_imagenet"
     ta_num_bins: int = 31
+    ra_num_ops: int = 2
+    ra_magnitude: int = 9
 
 
 def mix_options(d: DataConfig) -> Dict[str, Any]:
@@ -154,11 +159,16 @@ def mixes_batches(d: DataConfig) -> bool:
 
 
 def auto_augment_options(d: DataConfig) -> Dict[str, Any]:
-    """The native trainer's ``auto_augment`` / ``ta_num_bins`` from ``cfg.data``, validated (ValueError: an
-    unknown policy name, fewer than two bins)."""
+    """The native trainer's ``auto_augment`` / ``ta_num_bins`` / ``ra_num_ops`` / ``ra_magnitude`` from
+    ``cfg.data``, validated (ValueError: an unknown policy name, fewer than two bins, ``ra_num_ops`` outside 1..4,
+    ``ra_magnitude`` outside [0, ta_num_bins), an ``ra_*`` option set while the policy is not ``ra``). The two
+    ``ra_*`` arguments are passed with ``ra`` only: elsewhere they are at their defaults, or this raised."""
     from .engine.mix import validate_auto_augment
-    validate_auto_augment(d.auto_augment, d.ta_num_bins)
-    return dict(auto_augment=d.auto_augment, ta_num_bins=d.ta_num_bins)
+    validate_auto_augment(d.auto_augment, d.ta_num_bins, d.ra_num_ops, d.ra_magnitude)
+    kw = dict(auto_augment=d.auto_augment, ta_num_bins=d.ta_num_bins)
+    if d.auto_augment == "ra":
+        kw.update(ra_num_ops=d.ra_num_ops, ra_magnitude=d.ra_magnitude)
+    return kw
 
 
 LOSSES = ("ce", "bce")

@@ -228,7 +228,7 @@ PYBIND11_MODULE(_C, m) {
   DBX_BIND(augment_mix_u8);
   DBX_BIND(crop_resize_u8);
   DBX_BIND(ta_prepare);
-  DBX_BIND(ta_apply_u8);
+  DBX_BIND(ta_apply_u8);  // (with T_out: dbx_ta_stage_u8 -- the module exports the names it exported)
   DBX_BIND(mnist_fwd);
   DBX_BIND(mnist_bwd);
   DBX_BIND(colsum);

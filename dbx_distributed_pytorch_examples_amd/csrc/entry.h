@@ -116,7 +116,11 @@ int dbx_ta_prepare(const int* hist, const int* ops, unsigned char* lut, int* tme
 int dbx_ta_apply_u8(const unsigned char* T, bf16* out, const int* ops, const unsigned char* lut, const int* tmean,
                     int N, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1, float s2, const int* perm,
                     const int* mixbox, const float* blend, const int* erase, int pixel, unsigned long long seed,
-                    const int* rng_offset, hipStream_t st);
+                    const int* rng_offset, hipStream_t st, unsigned char* T_out, int* hist_out);
+// one operation of a chain: T_in -> T_out (R, G, B, L; not aliased) by ops, T_out's histograms added to hist. Python
+// reaches it through ta_apply_u8's binding: a non-null T_out there forwards here (out and the mixing arguments unread)
+int dbx_ta_stage_u8(const unsigned char* T_in, unsigned char* T_out, int* hist, const int* ops,
+                    const unsigned char* lut, const int* tmean, int N, int Ho, int Wo, hipStream_t st);
 
 // ---- classifier head (head_ops.hip) -----------------------------------------------------------------------------
 int dbx_small_gemm(int ta, int tb, int out_f32, int drop, const dbx::GemmArgs* args, hipStream_t st);

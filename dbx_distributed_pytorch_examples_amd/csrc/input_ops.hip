@@ -8,6 +8,8 @@
 //   augment_mix_u8   its mixing form: the MixUp blend and random erasing on top
 //   crop_resize_u8, ta_prepare, ta_apply_u8
 //                    TrivialAugmentWide between the crop and the normalisation (see the section below)
+//   ta_stage_u8      one more uint8 operation between ta_prepare and ta_apply_u8: the chains of RandAugment and
+//                    AutoAugment
 //
 // Mixing (augment_mix_u8 and ta_apply_u8). With f_s(oy, ox) the normalised fp32 pixel of source sample s --
 // the erase value where (oy, ox) lies in erase[s] = (y0, y1, x0, x1), output coordinates --
@@ -586,6 +588,54 @@ __global__ __launch_bounds__(256) void ta_apply_u8_kernel(const unsigned* __rest
   }
 }
 
+// ----------------------------------------------------------------------------------------
+// ta_stage_u8: one operation of a chain (RandAugment, AutoAugment). T_in -> T_out, both (R, G, B, L): sample n's
+// own operation through the same ta_row, L recomputed from the new pixel with crop_resize_u8's expression, and
+// T_out's histograms ADDED to hist -- what the next ta_prepare and the next operation read. The shape is
+// crop_resize_u8's (a block takes kTaRows rows of one sample; one LDS histogram and one integer-atomic flush per
+// chunk), the row walk ta_apply_u8's (tiles of kTile columns, the LUT staged for kinds >= 10 only). The affine
+// kinds and Sharpness read T_in outside the block's rows: T_out must not alias T_in.
+// ----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void ta_stage_u8_kernel(const unsigned* __restrict__ T_in, unsigned* __restrict__ T_out,
+                                                          int* __restrict__ hist, const int* __restrict__ ops,
+                                                          const unsigned char* __restrict__ lut,
+                                                          const int* __restrict__ tmean, int N, int Ho, int Wo) {
+  __shared__ unsigned arow[kTile];
+  __shared__ __attribute__((aligned(4))) unsigned char slut[768];
+  __shared__ int sh[4 * 256];
+  const int cps = (Ho + kTaRows - 1) / kTaRows;  // chunks per sample
+  for (int chunk = blockIdx.x; chunk < N * cps; chunk += gridDim.x) {
+    const int n = chunk / cps, r0 = (chunk - n * cps) * kTaRows, r1 = min(r0 + kTaRows, Ho);
+    for (int i = threadIdx.x; i < 4 * 256; i += blockDim.x) sh[i] = 0;
+    const TaSrc S = ta_src(ops, tmean, n);
+    if (S.kind >= 10)  // (block-uniform)
+      for (int i = threadIdx.x; i < 192; i += blockDim.x)
+        reinterpret_cast<unsigned*>(&slut[0])[i] = reinterpret_cast<const unsigned*>(lut + (size_t)n * 768)[i];
+    __syncthreads();
+    for (int oy = r0; oy < r1; ++oy) {
+      for (int x0 = 0; x0 < Wo; x0 += kTile) {
+        const int x1 = min(x0 + kTile, Wo);
+        ta_row(S, T_in, &slut[0], oy, Ho, Wo, x0, x1, &arow[0]);
+        __syncthreads();
+        for (int ox = x0 + threadIdx.x; ox < x1; ox += blockDim.x) {
+          const unsigned q = arow[ox - x0];
+          const int r = q & 255u, g = (q >> 8) & 255u, b = (q >> 16) & 255u;
+          const int L = (19595 * r + 38470 * g + 7471 * b + 0x8000) >> 16;  // <= 255
+          T_out[((size_t)n * Ho + oy) * Wo + ox] = q | ((unsigned)L << 24);
+          atomicAdd(&sh[r], 1);
+          atomicAdd(&sh[256 + g], 1);
+          atomicAdd(&sh[512 + b], 1);
+          atomicAdd(&sh[768 + L], 1);
+        }
+        __syncthreads();  // arow reuse by the next tile / row; the histogram is complete after the last
+      }
+    }
+    for (int i = threadIdx.x; i < 4 * 256; i += blockDim.x)
+      if (sh[i]) atomicAdd(&hist[(size_t)n * 1024 + i], sh[i]);
+    __syncthreads();  // sh and slut are rewritten by the next chunk
+  }
+}
+
 }  // namespace dbx
 
 using namespace dbx;
@@ -631,9 +681,17 @@ extern "C" int dbx_ta_prepare(const int* hist, const int* ops, unsigned char* lu
 extern "C" int dbx_ta_apply_u8(const unsigned char* T, bf16* out, const int* ops, const unsigned char* lut,
                                const int* tmean, int N, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1,
                                float s2, const int* perm, const int* mixbox, const float* blend, const int* erase,
-                               int pixel, unsigned long long seed, const int* rng_offset, hipStream_t st) {
+                               int pixel, unsigned long long seed, const int* rng_offset, hipStream_t st,
+                               unsigned char* T_out, int* hist_out) {
+  if (T_out) return dbx_ta_stage_u8(T, T_out, hist_out, ops, lut, tmean, N, Ho, Wo, st);
   const AugMix am{blend, erase, rng_offset, seed, pixel};
   hipLaunchKernelGGL(ta_apply_u8_kernel, row_grid(N * Ho), row_block(Wo), 0, st, (const unsigned*)T, out, ops, lut, tmean,
                      N, Ho, Wo, m0, m1, m2, s0, s1, s2, perm, mixbox, am);
+  RET_LAST;
+}
+extern "C" int dbx_ta_stage_u8(const unsigned char* T_in, unsigned char* T_out, int* hist, const int* ops,
+                               const unsigned char* lut, const int* tmean, int N, int Ho, int Wo, hipStream_t st) {
+  hipLaunchKernelGGL(ta_stage_u8_kernel, row_grid((long long)N * ((Ho + kTaRows - 1) / kTaRows)), row_block(Wo), 0, st,
+                     (const unsigned*)T_in, (unsigned*)T_out, hist, ops, lut, tmean, N, Ho, Wo);
   RET_LAST;
 }

@@ -3,8 +3,8 @@
 CPU-side, torchvision-compatible semantics for the transforms the reference uses
 (`utils/hf_dataset_utilities.py:58-81`, `03_composer/01_cifar_composer_resnet.ipynb:207-215`,
 `02_deepspeed/03_1k_imagenet_deepspeed_resnet.py:43-53`): Compose, Resize, CenterCrop,
-RandomCrop(pad), RandomResizedCrop, RandomHorizontalFlip, TrivialAugmentWide, Grayscale, ToTensor, Normalize,
-Lambda.
+RandomCrop(pad), RandomResizedCrop, RandomHorizontalFlip, TrivialAugmentWide, RandAugment, AutoAugment, Grayscale,
+ToTensor, Normalize, Lambda.
 Inputs: PIL images or uint8 HWC numpy arrays.
 
 For the native engine the heavy per-sample work moves to the GPU instead: the loader ships
@@ -210,6 +210,57 @@ class TrivialAugmentWide:
         if kind == 13:
             return ImageOps.equalize(img)
         raise ValueError(f"unknown TrivialAugmentWide kind {kind}")
+
+
+def _apply_chain(img, rows):
+    """``rows`` int32 [K, 8]: :meth:`TrivialAugmentWide.apply` folded over the K rows, in order."""
+    for row in np.asarray(rows, dtype=np.int32).reshape(-1, 8):
+        img = TrivialAugmentWide.apply(img, row)
+    return _to_pil(img).convert("RGB")
+
+
+class RandAugment:
+    """torchvision's ``RandAugment(num_ops=2, magnitude=9, num_magnitude_bins=31)`` on PIL images (nearest
+    interpolation, black fill): ``num_ops`` operations in sequence, each a uniform choice of the fourteen at the
+    fixed bin ``magnitude``. :meth:`apply` folds :meth:`TrivialAugmentWide.apply` over the rows of one sample of
+    the native engine's chain table (``engine.mix.sample_rand_augment``): the Pillow oracle of
+    ``K.chain_augment_u8``."""
+
+    def __init__(self, num_ops: int = 2, magnitude: int = 9, num_bins: int = 31):
+        from ..engine.mix import validate_auto_augment
+        validate_auto_augment("ra", num_bins, num_ops, magnitude)
+        self.num_ops, self.magnitude, self.num_bins = num_ops, magnitude, num_bins
+
+    def __call__(self, img):
+        from ..engine.mix import TA_KINDS, ra_table
+        img = _to_pil(img)
+        kind = [random.randrange(TA_KINDS) for _ in range(self.num_ops)]
+        sign = [random.randrange(2) for _ in range(self.num_ops)]
+        return self.apply(img, ra_table(kind, [self.magnitude] * self.num_ops, sign, img.size[1], img.size[0],
+                                        self.num_bins))
+
+    apply = staticmethod(_apply_chain)
+
+
+class AutoAugment:
+    """torchvision's ``AutoAugment(AutoAugmentPolicy.IMAGENET)`` on PIL images: one of 25 sub-policies per image,
+    each of its two operations applied with its probability (``engine.mix.AA_IMAGENET`` / ``aa_table``; Invert is
+    Solarize at threshold 0). :meth:`apply` as :class:`RandAugment`'s."""
+
+    def __init__(self, policy: str = "imagenet"):
+        if policy != "imagenet":
+            raise ValueError(f'only the "imagenet" policy is built, got {policy!r}')
+        self.policy = policy
+
+    def __call__(self, img):
+        from ..engine.mix import AA_IMAGENET, aa_table
+        img = _to_pil(img)
+        sub = [random.randrange(len(AA_IMAGENET))]
+        u = [[random.random()], [random.random()]]
+        sign = [[random.randrange(2)], [random.randrange(2)]]
+        return self.apply(img, aa_table(sub, u, sign, img.size[1], img.size[0])[:, 0])
+
+    apply = staticmethod(_apply_chain)
 
 
 class Grayscale:

@@ -37,7 +37,7 @@ from ..parallel.dist import host_sync_for_gloo
 from ..utils import debug as _debug
 from ..utils.profiling import PhaseTimer
 from .hyper import DeviceHyper
-from .mix import MixDraw, MixSampler, validate_auto_augment, validate_mix
+from .mix import MixDraw, MixSampler, auto_augment_stages, validate_auto_augment, validate_mix
 from .program import ResNetProgram, release_dead_graphs
 
 
@@ -83,11 +83,12 @@ class NativeTrainer:
                  mix_switch_prob: float = 0.5, erase_prob: float = 0.0, erase_mode: str = "const",
                  erase_scale: Tuple[float, float] = (0.02, 1 / 3), erase_ratio: Tuple[float, float] = (0.3, 3.3),
                  auto_augment: Optional[str] = None, ta_num_bins: int = 31, loss: str = "ce",
-                 bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False):
+                 bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False,
+                 ra_num_ops: int = 2, ra_magnitude: int = 9):
         validate_loss(loss, bce_target_threshold, bce_sum_classes)
         validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, erase_mode, erase_scale,
                      erase_ratio)
-        validate_auto_augment(auto_augment, ta_num_bins)
+        validate_auto_augment(auto_augment, ta_num_bins, ra_num_ops, ra_magnitude)
         if auto_augment is not None and model.conv1.in_channels != 3:
             raise ValueError(f"auto_augment={auto_augment!r} needs 3-channel images, the model takes "
                              f"{model.conv1.in_channels}")
@@ -135,6 +136,8 @@ class NativeTrainer:
         # chosen sample before any mixing. Sampling: engine/mix.py; the kernel: K.augment_u8.
         # auto_augment="ta_wide" (TrivialAugmentWide): one of fourteen uint8-space operations per sample, drawn
         # per step into a table that rides in the same arena; the input then runs K.trivial_augment_u8.
+        # "ra" (RandAugment) / "aa_imagenet" (AutoAugment's ImageNet policy): K operations in sequence per sample,
+        # a stage-major table [K, N, 8] in the same arena region; the input runs K.chain_augment_u8.
         self.cutmix_alpha = float(cutmix_alpha)
         self.mixup_alpha, self.erase_prob, self.erase_mode = float(mixup_alpha), float(erase_prob), erase_mode
         rng_seed = seed + 7919 * (dist.get_rank(process_group) if self.world > 1 else 0)
@@ -144,11 +147,12 @@ class NativeTrainer:
         self.auto_augment = auto_augment
         if self.cutmix_alpha > 0 or self.mixup_alpha > 0 or self.erase_prob > 0 or auto_augment is not None:
             self.prog.enable_mix(blend=self.mixup_alpha > 0, erase=self.erase_prob > 0, erase_mode=erase_mode,
-                                 seed=rng_seed, ta=auto_augment is not None)
+                                 seed=rng_seed, ta=auto_augment_stages(auto_augment, ra_num_ops))
             self._mix = MixSampler(self._rng, self.prog.N, self.prog.H, self.prog.W, mixup_alpha=mixup_alpha,
                                    cutmix_alpha=cutmix_alpha, mix_prob=mix_prob, mix_switch_prob=mix_switch_prob,
                                    erase_prob=erase_prob, erase_scale=erase_scale, erase_ratio=erase_ratio,
-                                   auto_augment=auto_augment, ta_num_bins=ta_num_bins)
+                                   auto_augment=auto_augment, ta_num_bins=ta_num_bins, ra_num_ops=ra_num_ops,
+                                   ra_magnitude=ra_magnitude)
         n = self.prog.n_params
         self.mom = torch.zeros(n, device=device)
         self.mom2 = torch.zeros(n, device=device) if optim.name in ("adam", "adamw", "lamb") else None
@@ -686,7 +690,7 @@ class NativeTrainer:
             N = p.N
             if self._mix_ring is None:
                 cuda = self.dev.type == "cuda"
-                words = p.mix_arena.numel()  # (5 N + 6, and 8 N more with the TrivialAugmentWide table)
+                words = p.mix_arena.numel()  # (5 N + 6, and 8 N more per stage of the auto-augment table)
                 self._mix_ring = [(torch.zeros(words, dtype=torch.int32).pin_memory() if cuda
                                    else torch.zeros(words, dtype=torch.int32),
                                    torch.cuda.Event() if cuda else None) for _ in range(4)]
@@ -728,7 +732,10 @@ class NativeTrainer:
                 "erase_prob": self.erase_prob, "erase_mode": self.erase_mode,
                 "erase_scale": m.erase_scale if m else None, "erase_ratio": m.erase_ratio if m else None,
                 "auto_augment": self.auto_augment, "ta_num_bins": m.ta_num_bins if m else 31,
-                "kernel": ("trivial_augment_u8" if self.prog.ta_ops is not None else
+                **({"num_ops": self.prog.ta_stages, "magnitude": m.ra_magnitude if self.auto_augment == "ra" else None}
+                   if self.auto_augment in ("ra", "aa_imagenet") else {}),
+                "kernel": ("chain_augment_u8" if self.prog.ta_stages > 1 else
+                           "trivial_augment_u8" if self.prog.ta_ops is not None else
                            "augment_mix_u8" if self.prog.mix_blend is not None else "augment_u8")}
 
     def _set_hyper(self, boundary: bool = True):

@@ -660,9 +660,11 @@ class ResNetProgram:
         # Philox offset of the "pixel" erase noise, consumed by the mixing form of the augment kernel
         self.mix_blend = self.erase_box = self.erase_off = self._erase_ctr = self.mix_arena = None
         self.erase_mode, self.erase_seed = "const", 0
-        # TrivialAugmentWide (enable_mix(ta=True)): the per-sample op table (a view of the arena) and the work
-        # buffer of K.trivial_augment_u8 (T, histograms, LUTs, gray means)
+        # TrivialAugmentWide (enable_mix(ta=1)): the per-sample op table (a view of the arena) and the work
+        # buffer of K.trivial_augment_u8 (T, histograms, LUTs, gray means); ta=K > 1 (RandAugment, AutoAugment):
+        # the stage-major chain table [K, N, 8] and the work buffer of K.chain_augment_u8
         self.ta_ops = self.ta_work = self.ta_T = self.ta_hist = self.ta_lut = self.ta_mean = None
+        self.ta_stages = 0
 
     def _pack_wdesc(self, descs) -> torch.Tensor:
         return K.pack_wdesc(descs, self.dev)
@@ -730,17 +732,22 @@ class ResNetProgram:
         return self.fuse_fin and bn.fin_f is not None
 
     def enable_mix(self, blend: bool = False, erase: bool = False, erase_mode: str = "const", seed: int = 0,
-                   ta: bool = False) -> None:
+                   ta: int = 0) -> None:
         """Batch mixing and erasing in the training-mode input kernel: the CutMix state, plus -- with
         ``blend`` (MixUp) or ``erase`` -- the blend weight ``mix_blend`` (fp32[1], 1 = no blend), the
         per-source-sample boxes ``erase_box`` (int32 [N, 4], empty = not erased) and the Philox offset
         ``erase_off`` of the "pixel" erase noise, which the step's weight-prep launch advances by one.
         The trainer writes them per step; evaluation never reads them.
 
-        ``ta`` (TrivialAugmentWide): the arena grows by the op table ``ta_ops`` (int32 [N, 8], all zero =
-        Identity), the program owns the work buffer of ``K.trivial_augment_u8`` (``ta_T``, ``ta_hist``,
-        ``ta_lut``, ``ta_mean`` are its views) and the training-mode input runs that pipeline. 3-channel
-        programs only."""
+        ``ta`` (the stage count; True = 1, TrivialAugmentWide): the arena grows by the op table ``ta_ops`` (int32
+        [N, 8], all zero = Identity), the program owns the work buffer of ``K.trivial_augment_u8`` (``ta_T``,
+        ``ta_hist``, ``ta_lut``, ``ta_mean`` are its views) and the training-mode input runs that pipeline. With
+        ``ta`` = K in 2..4 (RandAugment, AutoAugment) the table is the stage-major chain [K, N, 8] -- still one
+        region of the arena, one copy per step -- the work buffer holds two T and K histogram sets, and the input
+        runs ``K.chain_augment_u8``. 3-channel programs only."""
+        ta = int(ta)
+        if not 0 <= ta <= 4:
+            raise ValueError(f"ta (operations in sequence per sample) must be in 0..4, got {ta}")
         if erase_mode not in ("const", "pixel"):
             raise ValueError(f'erase_mode must be "const" or "pixel", got {erase_mode!r}')
         if ta and self.in_ch != 3:
@@ -749,10 +756,10 @@ class ResNetProgram:
         self.enable_cutmix()
         if not (blend or erase or ta):
             return
-        # one int32 arena [perm N | box 4 | lam 1 | blend 1 | erase 4 N | ta 8 N] that the trainer refreshes with
+        # one int32 arena [perm N | box 4 | lam 1 | blend 1 | erase 4 N | ta 8 K N] that the trainer refreshes with
         # ONE host-to-device copy per step; the tensors the kernels take are views of it (lam / blend: fp32 bits)
         N = self.N
-        self.mix_arena = a = torch.zeros((13 if ta else 5) * N + 6, device=dev, dtype=torch.int32)
+        self.mix_arena = a = torch.zeros((5 + 8 * ta) * N + 6, device=dev, dtype=torch.int32)
         a[:N] = self.mix_perm
         self.mix_perm, self.mix_box = a[:N], a[N:N + 4]
         self.mix_lam, self.mix_blend = a[N + 4:N + 5].view(torch.float32), a[N + 5:N + 6].view(torch.float32)
@@ -760,9 +767,10 @@ class ResNetProgram:
         self.mix_blend.fill_(1.0)
         self.erase_box = a[N + 6:5 * N + 6].view(N, 4)
         if ta:
-            self.ta_ops = a[5 * N + 6:].view(N, 8)
-            self.ta_work = torch.zeros(K.ta_work_words(N, self.H, self.W), device=dev, dtype=torch.int32)
-            self.ta_T, self.ta_hist, self.ta_lut, self.ta_mean = K.ta_work_views(self.ta_work, N, self.H, self.W)
+            self.ta_stages = ta
+            self.ta_ops = a[5 * N + 6:].view(N, 8) if ta == 1 else a[5 * N + 6:].view(ta, N, 8)
+            self.ta_work = torch.zeros(K.ta_work_words(N, self.H, self.W, ta), device=dev, dtype=torch.int32)
+            self.ta_T, self.ta_hist, self.ta_lut, self.ta_mean = K.ta_work_views(self.ta_work, N, self.H, self.W, ta)
         self.erase_mode, self.erase_seed = erase_mode, int(seed) & (2 ** 64 - 1)
         # an int64 counter (the weight-prep launch's counter entry adds 1 to int64s); the kernel reads
         # its low word, an int32 that wraps
@@ -825,7 +833,9 @@ class ResNetProgram:
             if self.ta_ops is not None or self.mix_blend is not None:  # the mixing arena: blend, erasing
                 kw.update(blend=self.mix_blend, erase=self.erase_box, erase_mode=self.erase_mode,
                           erase_rng=(self.erase_seed, self.erase_off))
-        if mix and self.ta_ops is not None:
+        if mix and self.ta_stages > 1:
+            K.chain_augment_u8(self.img_u8, self.x4, self.boxes, mean, std, flip, self.ta_ops, self.ta_work, **kw)
+        elif mix and self.ta_ops is not None:
             K.trivial_augment_u8(self.img_u8, self.x4, self.boxes, mean, std, flip, self.ta_ops, self.ta_work, **kw)
         else:
             K.augment_u8(self.img_u8, self.x4, self.boxes, mean, std, flip, **kw)

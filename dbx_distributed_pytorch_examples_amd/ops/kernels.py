@@ -1722,8 +1722,8 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *,
         C().augment_mix_u8(*args, *mix, stream_ptr())
 
 
-ta_work_words = _ref.ta_work_words  # int32 words of trivial_augment_u8's work buffer for (N, Ho, Wo)
-ta_work_views = _ref.ta_work_views  # its (T, hist, lut, mean) views
+ta_work_words = _ref.ta_work_words  # int32 words of trivial_augment_u8's work buffer for (N, Ho, Wo); with stages=K
+ta_work_views = _ref.ta_work_views  # of chain_augment_u8's. Its (T, hist, lut, mean) views
 
 
 @_dispatch
@@ -1779,7 +1779,7 @@ def ta_apply_u8(T, out, ops, lut, tmean, mean, std, *, perm=None, mixbox=None, b
         raise ValueError("T: expected [N, Ho, Wo, 4] uint8; T and lut 4-byte aligned")
     mix = _mix_args(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
     C().ta_apply_u8(T.data_ptr(), out.data_ptr(), ops.data_ptr(), lut.data_ptr(), tmean.data_ptr(), N, Ho, Wo,
-                    *_norm6(mean, std), *mix, stream_ptr())
+                    *_norm6(mean, std), *mix, stream_ptr(), 0, 0)
 
 
 def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None, erase=None,
@@ -1800,6 +1800,55 @@ def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None
     ta_prepare(hist, ops, lut, tmean)
     ta_apply_u8(T, out, ops, lut, tmean, mean, std, perm=perm, mixbox=mixbox, blend=blend, erase=erase,
                 erase_mode=erase_mode, erase_rng=erase_rng)
+
+
+@_dispatch
+def ta_stage_u8(T_in, T_out, hist_out, ops, lut, tmean):
+    """One operation of a chain: ``T_in`` uint8 [N, Ho, Wo, 4] -> ``T_out`` of the same layout, per sample the
+    operation of its row of ``ops`` (with ``lut`` / ``tmean`` from :func:`ta_prepare` on ``T_in``'s histograms):
+    R, G, B as :func:`ta_apply_u8` computes them before it normalises, L Pillow's gray value of the new pixel.
+    ADDS ``T_out``'s per-sample histograms to ``hist_out`` int32 [N, 4, 256] (the caller zeroes it). The
+    operation is sample n's own: no mixing, erasing or normalisation here. ValueError: ``T_out`` overlapping
+    ``T_in``, a misaligned ``T`` or ``lut``."""
+    N, Ho, Wo = _ref.check_ta_stage(T_in, T_out, hist_out, ops, lut, tmean)
+    _chk(T_in, torch.uint8, "T_in")
+    _chk(T_out, torch.uint8, "T_out", N * Ho * Wo * 4)
+    _chk(hist_out, torch.int32, "hist_out", N * 1024)
+    _chk(ops, torch.int32, "ops", N * 8)
+    _chk(lut, torch.uint8, "lut", N * 768)
+    _chk(tmean, torch.int32, "tmean", N)
+    if T_in.data_ptr() % 4 or T_out.data_ptr() % 4 or lut.data_ptr() % 4:
+        raise ValueError("T_in, T_out and lut must be 4-byte aligned")
+    # csrc/entry.h dbx_ta_stage_u8, through the ta_apply_u8 binding (the extension exports the names it exported): a
+    # T_out there launches the stage kernel; the output, the normalisation and the mixing arguments are unread
+    C().ta_apply_u8(T_in.data_ptr(), 0, ops.data_ptr(), lut.data_ptr(), tmean.data_ptr(), N, Ho, Wo,
+                    0.0, 0.0, 0.0, 1.0, 1.0, 1.0, 0, 0, 0, 0, 0, 0, 0, stream_ptr(), T_out.data_ptr(), hist_out.data_ptr())
+
+
+def chain_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None, erase=None,
+                     erase_mode="const", erase_rng=None):
+    """:func:`trivial_augment_u8` for a table with a stage axis (RandAugment, AutoAugment): ``ops`` int32
+    [K, N, 8], stage-major, 1 <= K <= 4, applies K operations in sequence to each sample, every one on the
+    uint8 output of the one before and with that image's own histograms, gray value and gray mean. ``work``: at
+    least ``ta_work_words(N, Ho, Wo, K)`` words. 2 K + 1 launches and one memset of all K histogram sets:
+    :func:`crop_resize_u8`; K - 1 times :func:`ta_prepare` + :func:`ta_stage_u8`; :func:`ta_prepare`;
+    :func:`ta_apply_u8` with the last stage's operation and the erasing / mixing arguments. K = 1 issues the
+    launches of ``trivial_augment_u8``. ValueError, before any launch: ``Cin != 3``, K outside 1..4, a table
+    that is not [K, N, 8], a work buffer that is too small."""
+    N, Ho, Wo, _ = out.shape
+    if img.shape[3] != 3:
+        raise ValueError(f"chain_augment_u8 takes 3-channel images, got Cin={img.shape[3]}")
+    Kst = _ref.check_chain_ops(ops, N)
+    T, hist, lut, tmean = _ref.ta_work_views(work, N, Ho, Wo, Kst)
+    T, hists = T.view(-1, N, Ho, Wo, 4), hist.view(Kst, N, 4, 256)
+    hist.zero_()
+    crop_resize_u8(img, T[0], hists[0], boxes, flip)
+    for i in range(Kst - 1):
+        ta_prepare(hists[i], ops[i], lut, tmean)
+        ta_stage_u8(T[i & 1], T[(i + 1) & 1], hists[i + 1], ops[i], lut, tmean)
+    ta_prepare(hists[Kst - 1], ops[Kst - 1], lut, tmean)
+    ta_apply_u8(T[(Kst - 1) & 1], out, ops[Kst - 1], lut, tmean, mean, std, perm=perm, mixbox=mixbox, blend=blend,
+                erase=erase, erase_mode=erase_mode, erase_rng=erase_rng)
 
 
 def pack_wdesc(descs, device) -> torch.Tensor:

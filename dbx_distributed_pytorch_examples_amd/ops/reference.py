@@ -1006,23 +1006,40 @@ TA_NAMES = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate"
             "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")
 
 
-def ta_work_words(N: int, Ho: int, Wo: int) -> int:
+TA_MAX_STAGES = 4  # operations in sequence per sample (chain_augment_u8)
+
+
+def check_ta_stages(stages) -> int:
+    if isinstance(stages, bool) or not isinstance(stages, int) or not 1 <= stages <= TA_MAX_STAGES:
+        raise ValueError(f"stages must be an integer in 1..{TA_MAX_STAGES}, got {stages!r}")
+    return stages
+
+
+def ta_work_words(N: int, Ho: int, Wo: int, stages: int = 1) -> int:
     """int32 words of the pipeline's work buffer: T [N, Ho, Wo, 4] uint8 | histograms [N, 4, 256] int32 |
-    lut [N, 3, 256] uint8 | mean [N] int32."""
-    return N * Ho * Wo + N * 1024 + N * 192 + N
+    lut [N, 3, 256] uint8 | mean [N] int32. A chain of ``stages`` > 1 operations (``chain_augment_u8``) holds two
+    T (read and written in turn) and one histogram set per stage; lut and mean are reused."""
+    stages = check_ta_stages(stages)
+    return (2 if stages > 1 else 1) * N * Ho * Wo + stages * N * 1024 + N * 192 + N
 
 
-def ta_work_views(work, N: int, Ho: int, Wo: int):
-    """(T, hist, lut, mean) views of an int32 work buffer of at least :func:`ta_work_words` words."""
+def ta_work_views(work, N: int, Ho: int, Wo: int, stages: int = 1):
+    """(T, hist, lut, mean) views of an int32 work buffer of at least :func:`ta_work_words` words. With
+    ``stages`` > 1: T is [2, N, Ho, Wo, 4] and hist [stages, N, 4, 256] (contiguous: one memset zeroes all)."""
     if work.dtype != torch.int32:
         raise TypeError(f"work: expected torch.int32, got {work.dtype}")
-    need = ta_work_words(N, Ho, Wo)
+    need = ta_work_words(N, Ho, Wo, stages)
     if work.numel() < need or not work.is_contiguous():
-        raise ValueError(f"work: needs {need} contiguous int32 words for N={N}, {Ho}x{Wo}, got {work.numel()}")
+        raise ValueError(f"work: needs {need} contiguous int32 words for N={N}, {Ho}x{Wo}"
+                         f"{f', {stages} stages' if stages > 1 else ''}, got {work.numel()}")
     w = work.view(-1)
-    a = N * Ho * Wo
-    return (w[:a].view(torch.uint8).view(N, Ho, Wo, 4), w[a:a + N * 1024].view(N, 4, 256),
-            w[a + N * 1024:a + N * 1216].view(torch.uint8).view(N, 3, 256), w[a + N * 1216:a + N * 1217])
+    nt = 2 if stages > 1 else 1
+    a = nt * N * Ho * Wo
+    b = a + stages * N * 1024
+    T, hist = w[:a].view(torch.uint8), w[a:b]
+    T, hist = (T.view(N, Ho, Wo, 4), hist.view(N, 4, 256)) if stages == 1 else (T.view(2, N, Ho, Wo, 4),
+                                                                                hist.view(stages, N, 4, 256))
+    return T, hist, w[b:b + N * 192].view(torch.uint8).view(N, 3, 256), w[b + N * 192:b + N * 193]
 
 
 def check_ta_ops(ops, N: int):
@@ -1222,6 +1239,69 @@ def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None
     ta_prepare(hist, ops, lut, tmean)
     ta_apply_u8(T, out, ops, lut, tmean, mean, std, perm=perm, mixbox=mixbox, blend=blend, erase=erase,
                 erase_mode=erase_mode, erase_rng=erase_rng)
+
+
+def check_ta_stage(T_in, T_out, hist_out, ops, lut, tmean):
+    """The argument rules of ``ta_stage_u8`` (shared by the kernel wrapper and the CPU path); returns
+    ``(N, Ho, Wo)``. ValueError: shapes that disagree, ``T_out`` overlapping ``T_in`` (the affine kinds and
+    Sharpness read ``T_in`` at other rows than the one being written)."""
+    for nm, t, dt in (("T_in", T_in, torch.uint8), ("T_out", T_out, torch.uint8), ("hist_out", hist_out, torch.int32),
+                      ("lut", lut, torch.uint8), ("tmean", tmean, torch.int32)):
+        if not isinstance(t, torch.Tensor) or t.dtype != dt:
+            raise TypeError(f"{nm}: expected a {dt} tensor, got {getattr(t, 'dtype', type(t))}")
+    if T_in.dim() != 4 or T_in.shape[3] != 4 or tuple(T_out.shape) != tuple(T_in.shape):
+        raise ValueError(f"T_in / T_out: expected two [N, Ho, Wo, 4] uint8 tensors of one shape, got "
+                         f"{tuple(T_in.shape)} and {tuple(T_out.shape)}")
+    N, Ho, Wo, _ = T_in.shape
+    check_ta_ops(ops, N)
+    _ta_sizes(N, hist=hist_out, lut=lut, tmean=tmean)
+    a0, b0 = T_in.data_ptr(), T_out.data_ptr()
+    if T_in.device == T_out.device and a0 < b0 + T_out.numel() and b0 < a0 + T_in.numel():
+        raise ValueError("T_out must not alias T_in: an operation reads rows of T_in other than the one it writes")
+    return N, Ho, Wo
+
+
+def ta_stage_u8(T_in, T_out, hist_out, ops, lut, tmean):
+    """One operation of a chain, the definition: ``T_out[n]`` = (R, G, B, L) of :func:`ta_apply_image` on
+    ``T_in[n]`` with row ``ops[n]`` (``lut`` / ``tmean`` from ``ta_prepare`` on ``T_in``'s histograms); ADDS
+    ``T_out``'s histograms to ``hist_out`` int32 [N, 4, 256]."""
+    N, Ho, Wo = check_ta_stage(T_in, T_out, hist_out, ops, lut, tmean)
+    a, o = T_in.numpy(), ops.numpy()
+    l, mn = lut.view(N, 3, 256).numpy(), tmean.view(-1).tolist()
+    for n in range(N):
+        T_out[n].copy_(ta_pack(ta_apply_image(a[n], o[n], l[n], mn[n])))
+    hist_out.add_(ta_histograms(T_out).view(hist_out.shape))
+
+
+def check_chain_ops(ops, N: int) -> int:
+    """The stage count K of a chain table int32 [K, N, 8] (stage-major: each stage's [N, 8] slice is a table of
+    the single-operation kernels)."""
+    if not isinstance(ops, torch.Tensor) or ops.dtype != torch.int32:
+        raise TypeError(f"ops: expected an int32 tensor [K, N, 8] (per stage: kind, p, a..f as fp32 bits), got "
+                        f"{getattr(ops, 'dtype', type(ops))}")
+    if ops.dim() != 3 or tuple(ops.shape[1:]) != (N, 8) or not ops.is_contiguous():
+        raise ValueError(f"ops: expected a contiguous table of shape (K, {N}, 8), got {tuple(ops.shape)}")
+    if not 1 <= ops.shape[0] <= TA_MAX_STAGES:
+        raise ValueError(f"ops: a chain has 1..{TA_MAX_STAGES} stages, got K={ops.shape[0]}")
+    return int(ops.shape[0])
+
+
+def chain_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None,
+                     erase=None, erase_mode="const", erase_rng=None):
+    N, Ho, Wo, _ = out.shape
+    if img.shape[3] != 3:
+        raise ValueError(f"chain_augment_u8 takes 3-channel images, got Cin={img.shape[3]}")
+    Kst = check_chain_ops(ops, N)
+    T, hist, lut, tmean = ta_work_views(work, N, Ho, Wo, Kst)
+    T, hist = T.view(-1, N, Ho, Wo, 4), hist.view(Kst, N, 4, 256)
+    hist.zero_()
+    crop_resize_u8(img, T[0], hist[0], boxes, flip)
+    for i in range(Kst - 1):
+        ta_prepare(hist[i], ops[i], lut, tmean)
+        ta_stage_u8(T[i & 1], T[(i + 1) & 1], hist[i + 1], ops[i], lut, tmean)
+    ta_prepare(hist[Kst - 1], ops[Kst - 1], lut, tmean)
+    ta_apply_u8(T[(Kst - 1) & 1], out, ops[Kst - 1], lut, tmean, mean, std, perm=perm, mixbox=mixbox, blend=blend,
+                erase=erase, erase_mode=erase_mode, erase_rng=erase_rng)
 
 
 def weight_prep(master, wbuf, desc_dev, nlayers):
