@@ -141,6 +141,10 @@ class DataConfig:
     ta_num_bins: int = 31
     ra_num_ops: int = 2
     ra_magnitude: int = 9
+    # repeated augmentation (DeiT / timm's RepeatAugSampler; A1 / A2 use 3): every drawn image appears aug_repeats
+    # times in a row in the epoch's order, each copy augmented on its own; the epoch keeps its length, so it visits
+    # about 1 / aug_repeats of the images. Map-style datasets only; validation never repeats.
+    aug_repeats: int = 1
 
 
 def mix_options(d: DataConfig) -> Dict[str, Any]:
@@ -196,12 +200,45 @@ def loss_options(d: DataConfig) -> Dict[str, Any]:
     return kw
 
 
+def validate_aug_repeats(aug_repeats: Any) -> int:
+    """ValueError unless ``aug_repeats`` is an integer >= 1 (refused, never ignored)."""
+    r = aug_repeats
+    if isinstance(r, bool) or not isinstance(r, int) or r < 1:
+        raise ValueError(f"aug_repeats must be an integer >= 1, got {r!r}")
+    return r
+
+
 def validate_data(d: DataConfig) -> None:
-    """ValueError for a bad batch-mixing, erasing, auto-augment or training-loss setting, whichever engine
-    would run."""
+    """ValueError for a bad batch-mixing, erasing, auto-augment, training-loss or repeated-augmentation setting,
+    whichever engine would run."""
     mix_options(d)
     auto_augment_options(d)
     loss_options(d)
+    validate_aug_repeats(d.aug_repeats)
+
+
+def validate_drop_path(rate: Any) -> float:
+    """ValueError unless the stochastic-depth rate is a number in [0, 1). Shared by the config and the trainers."""
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 <= float(rate) < 1.0:
+        raise ValueError(f"drop_path_rate must be a number in [0, 1), got {rate!r}")
+    return float(rate)
+
+
+def drop_path_probs(rate: float, nblocks: int) -> List[float]:
+    """timm's linear stochastic-depth rule over ``nblocks`` residual blocks: p_l = rate * l / (L - 1), in
+    float64 (Python floats). The first block is never dropped, the last one with probability ``rate``."""
+    rate = validate_drop_path(rate)
+    if nblocks < 1:
+        raise ValueError(f"drop_path_probs: {nblocks} blocks")
+    if nblocks == 1:
+        return [0.0]
+    return [rate * l / (nblocks - 1) for l in range(nblocks)]
+
+
+def validate_train(cfg: "TrainConfig") -> None:
+    """ValueError for a bad data setting (:func:`validate_data`) or stochastic-depth rate."""
+    validate_data(cfg.data)
+    validate_drop_path(cfg.drop_path_rate)
 
 
 @dataclass
@@ -213,6 +250,9 @@ class TrainConfig:
     ema_decay: float = 0.0             # weight EMA (native engine): 0 = off, else the decay d in [0, 1)
     ema_warmup: bool = False           # d_t = min(ema_decay, (1 + t) / (10 + t)) at optimizer step t
     ema_eval: bool = True              # val_* metrics from the averaged weights when ema_decay > 0
+    # stochastic depth, per batch (native engine): block l of L is dropped for a whole micro-batch with probability
+    # rate * l / (L - 1) and scaled by 1 / (1 - p_l) otherwise (timm's linear rule; A1 / A2 use 0.05). In [0, 1).
+    drop_path_rate: float = 0.0
     epochs: int = 1
     max_steps: int = 0                 # 0 = full epochs
     duration: str = ""                 # composer style: "2ep" / "100ba"

@@ -87,7 +87,10 @@ int dbx_adam(float* p, const float* g, float* m, float* v, bf16* p16, long long 
              hipStream_t st);
 int dbx_ema_update(float* e, const float* p, long long n, const float* omd_ptr, float omd, hipStream_t st);
 int dbx_ema_update_multi(const void* desc, int ntensors, long long max_len, const float* omd_ptr, float omd,
-                         hipStream_t st);  // desc: EmaDesc[ntensors]
+                         hipStream_t st, const float* gates);  // desc: EmaDesc[ntensors]
+// stochastic depth: y = gates[row.gate] * x per row of desc (GateDesc[nrows]; gates: device fp32). Python reaches it
+// through ema_update_multi's binding: non-null gates there forward here (desc a GateDesc table, omd unread)
+int dbx_gate_scale_multi(const void* desc, int nrows, long long max_len, const float* gates, hipStream_t st);
 int dbx_lars_scale(const float* p, float* g, const int* seg_off, const int* seg_len, const int* adapt, int nseg,
                    int max_len, double* norms, float gs, float eta, float wd, hipStream_t st);
 int dbx_lamb(float* p, float* g, float* m, float* v, bf16* p16, const int* seg_off, const int* seg_len,

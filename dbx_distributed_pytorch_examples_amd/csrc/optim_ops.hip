@@ -5,6 +5,7 @@
 //   lars_norms_kernel / lars_apply_kernel   LARS pre-scaling of the gradient, per parameter tensor
 //   lamb_moments_kernel / lamb_apply_kernel<EMA>   LAMB, per parameter tensor
 //   grad_accum_kernel, ema_kernel, sumsq_kernel, clip_factor_kernel
+//   gate_scale_kernel                       stochastic depth's per-block scalar over a table of rows
 //
 // Every piece the kernels share -- the EMA arguments, the group table in LDS and the lookup in it, the
 // four-lane EMA lerp, the bf16x4 store, the per-(segment, block) norm slots and their fixed-order sum -- is
@@ -415,6 +416,31 @@ __global__ void ema_kernel(const EmaDesc* __restrict__ desc, float* __restrict__
   for (long long k = n4 * 4 + tid; k < n; k += nth) e[k] = ema_lerp(e[k], p[k], omd);
 }
 
+// Stochastic depth's per-block scalar: y[i] = gates[row.gate] * x[i] for every row of a device table of
+// {dst address, src address, length, gate index} entries, grid (blocks, rows) as ema_kernel's table shape.
+// The gates are fp32 in device memory, so a replayed graph follows the values the host copied in. dst == src
+// is allowed (an element is read and written by one lane); partly overlapping rows are not. One fp32 multiply
+// per element, in the vector and the scalar loop alike (a product by itself has nothing to contract with).
+// Alignment policy of ema_kernel, per row. The host validates the gate index (ops/kernels.py pack_gate_desc).
+struct GateDesc { long long dst, src, len, gate; };
+static_assert(sizeof(GateDesc) == 32 && offsetof(GateDesc, gate) == 24, "GateDesc layout (ops/kernels.py pack_gate_desc)");
+__global__ void gate_scale_kernel(const GateDesc* __restrict__ desc, const float* __restrict__ gates) {
+  const GateDesc d = desc[blockIdx.y];
+  float* y = reinterpret_cast<float*>(d.dst);
+  const float* x = reinterpret_cast<const float*>(d.src);
+  const long long n = d.len;
+  const float m = gates[d.gate];
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long long nth = (long long)gridDim.x * blockDim.x;
+  const bool vec = ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(x)) & 15) == 0;
+  const long long n4 = vec ? n / 4 : 0;
+  for (long long i = tid; i < n4; i += nth) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(x + i * 4);
+    *reinterpret_cast<f32x4*>(y + i * 4) = f32x4{m * v[0], m * v[1], m * v[2], m * v[3]};
+  }
+  for (long long k = n4 * 4 + tid; k < n; k += nth) y[k] = m * x[k];
+}
+
 // sum of squares over a flat fp32 buffer (global-norm clipping), one fp64 atomic per block. fp64
 // sums of fp32 block partials are exact (hence independent of block order) while the partials'
 // magnitudes span less than ~2^29; beyond that the last bits of the norm can depend on the order.
@@ -505,11 +531,20 @@ extern "C" int dbx_ema_update(float* e, const float* p, long long n, const float
   RET_LAST;
 }
 extern "C" int dbx_ema_update_multi(const void* desc, int ntensors, long long max_len, const float* omd_ptr, float omd,
-                                    hipStream_t st) {
+                                    hipStream_t st, const float* gates) {
+  if (gates) return dbx_gate_scale_multi(desc, ntensors, max_len, gates, st);
   if (ntensors <= 0 || max_len <= 0) return 0;
   if (!desc || ntensors > 65535) return -1;
   hipLaunchKernelGGL(ema_kernel, dim3(grid_for((max_len + 3) / 4, 256, 64), ntensors), dim3(256), 0, st,
                      (const EmaDesc*)desc, (float*)nullptr, (const float*)nullptr, 0LL, omd_ptr, omd);
+  RET_LAST;
+}
+extern "C" int dbx_gate_scale_multi(const void* desc, int nrows, long long max_len, const float* gates,
+                                    hipStream_t st) {
+  if (nrows <= 0 || max_len <= 0) return 0;
+  if (!desc || !gates || nrows > 65535) return -1;
+  hipLaunchKernelGGL(gate_scale_kernel, dim3(grid_for((max_len + 3) / 4, 256, 64), nrows), dim3(256), 0, st,
+                     (const GateDesc*)desc, gates);
   RET_LAST;
 }
 // blocks per segment of the LARS / LAMB grids (the slots the second kernel reads are the ones the first wrote)

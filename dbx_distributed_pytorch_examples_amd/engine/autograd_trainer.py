@@ -239,7 +239,13 @@ class AutogradTrainer:
                  stage3: Optional[dict] = None, mixup_alpha: float = 0.0, mix_prob: float = 1.0,
                  mix_switch_prob: float = 0.5, erase_prob: float = 0.0, erase_mode: str = "const",
                  erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3), auto_augment=None, loss: str = "ce",
-                 bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False):
+                 bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False,
+                 drop_path_rate: float = 0.0):
+        from ..config import validate_drop_path
+        if validate_drop_path(drop_path_rate) != 0.0:  # refused, never ignored
+            raise ValueError(f"drop_path_rate={drop_path_rate!r} is built into the native training step (NativeTrainer: "
+                             f"gates on the blocks' last BatchNorm); the autograd engine runs the module as it is -- "
+                             f"put torchvision.ops.StochasticDepth into the model instead")
         if auto_augment is not None:  # refused, never ignored
             raise ValueError(f"auto_augment={auto_augment!r} runs in the native step's input kernels (NativeTrainer); "
                              f"the autograd engine has no such stage -- put data.transforms.TrivialAugmentWide in the "

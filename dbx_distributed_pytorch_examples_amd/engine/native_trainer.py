@@ -26,11 +26,13 @@ import os
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Tuple
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from ..config import distinct_param_groups, has_param_groups, resolve_param_groups, validate_loss
+from ..config import (distinct_param_groups, drop_path_probs, has_param_groups, resolve_param_groups,
+                      validate_drop_path, validate_loss)
 from ..engine_config import EngineConfig
 from ..ops import kernels as K
 from ..parallel.dist import host_sync_for_gloo
@@ -84,8 +86,9 @@ class NativeTrainer:
                  erase_scale: Tuple[float, float] = (0.02, 1 / 3), erase_ratio: Tuple[float, float] = (0.3, 3.3),
                  auto_augment: Optional[str] = None, ta_num_bins: int = 31, loss: str = "ce",
                  bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False,
-                 ra_num_ops: int = 2, ra_magnitude: int = 9):
+                 ra_num_ops: int = 2, ra_magnitude: int = 9, drop_path_rate: float = 0.0):
         validate_loss(loss, bce_target_threshold, bce_sum_classes)
+        self.drop_path_rate = validate_drop_path(drop_path_rate)
         validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, erase_mode, erase_scale,
                      erase_ratio)
         validate_auto_augment(auto_augment, ta_num_bins, ra_num_ops, ra_magnitude)
@@ -153,6 +156,20 @@ class NativeTrainer:
                                    erase_prob=erase_prob, erase_scale=erase_scale, erase_ratio=erase_ratio,
                                    auto_augment=auto_augment, ta_num_bins=ta_num_bins, ra_num_ops=ra_num_ops,
                                    ra_magnitude=ra_magnitude)
+        # stochastic depth, per batch (ResNetProgram.enable_drop_path): every step() call -- micro-steps too --
+        # draws u ~ U[0, 1) per gated block from a generator of its own (the mix sampler's sequences do not move),
+        # seeded like it by seed and rank: ranks drop different blocks, which is correct because a rank's gates
+        # scale its gradients before the collective sums them. The gates reach the device through a pinned ring.
+        self.drop_path_p = drop_path_probs(self.drop_path_rate, len(self.prog.blocks))
+        self.last_drop_path: Optional[dict] = None  # what the last step used: p, gates, dropped (gated blocks)
+        self._drop_rng = self._drop_dev = None
+        if self.drop_path_rate > 0:
+            self.prog.enable_drop_path(self.drop_path_p)
+        if self.prog.drop_gates is not None:
+            self._drop_rng = np.random.default_rng([rng_seed, 0x6470])  # ("dp": a stream apart from the mixing's)
+            self._drop_p = np.array([self.drop_path_p[l] for l in self.prog.drop_blocks], dtype=np.float64)
+            self._drop_keep = (1.0 / (1.0 - self._drop_p)).astype(np.float32)
+            self._drop_dev = DeviceHyper(self.prog.drop_gates)
         n = self.prog.n_params
         self.mom = torch.zeros(n, device=device)
         self.mom2 = torch.zeros(n, device=device) if optim.name in ("adam", "adamw", "lamb") else None
@@ -718,6 +735,23 @@ class NativeTrainer:
         for dst, src in host:
             dst.copy_(src, non_blocking=True)
 
+    def _sample_drop_path(self):
+        """This step's gates: block l is dropped (gate 0) when u < p_l, else kept with gate fl32(1 / (1 - p_l))."""
+        u = self._drop_rng.random(len(self._drop_p))
+        dropped = u < self._drop_p
+        gates = np.where(dropped, np.float32(0.0), self._drop_keep)
+        self.last_drop_path = {"p": self._drop_p.tolist(), "gates": [float(g) for g in gates],
+                               "dropped": [l for l, d in zip(self.prog.drop_blocks, dropped) if d]}
+        self._drop_dev.set(self.last_drop_path["gates"])
+
+    def drop_path_summary(self) -> dict:
+        """The stochastic-depth settings, for logging."""
+        gated = self.prog.drop_blocks
+        return {"drop_path_rate": self.drop_path_rate, "mode": "batch", "blocks": len(self.prog.blocks),
+                "gated_blocks": len(gated), "p_max": max(self.drop_path_p) if gated else 0.0,
+                "kernel": "gate_scale_multi" if gated else None,
+                "launches_per_step": (1 + len(self.prog._gate_bwd)) if gated else 0}
+
     def loss_summary(self) -> dict:
         """The training-loss settings, for logging."""
         return {"loss": self.loss, "label_smoothing": self.smoothing,
@@ -896,6 +930,8 @@ class NativeTrainer:
             p.flip.copy_(flips, non_blocking=True)
         if self._mix is not None:
             self._sample_mix()
+        if self._drop_rng is not None:
+            self._sample_drop_path()
         # gradient accumulation: every call but the window's last is a micro-step
         boundary = self.micro == self.k - 1
         self._set_hyper(boundary)

@@ -125,6 +125,10 @@ class BNL:
     beta: Optional[torch.Tensor] = None
     dgamma: Optional[torch.Tensor] = None
     dbeta: Optional[torch.Tensor] = None
+    # what the training-mode readers (forward finalize, backward coefficients) take: the master views above, or
+    # the gated copies of a block's last BN (ResNetProgram.enable_drop_path)
+    gamma_t: Optional[torch.Tensor] = None
+    beta_t: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -292,6 +296,10 @@ class ResNetProgram:
                 self.fold_min = 0
             if cfg.fold_max_ratio is None:
                 self.fold_max_ratio = 8.0
+        # stochastic depth (enable_drop_path): the gates, the gated BNs' effective parameters, the launch tables
+        self.drop_gates = self.drop_eff = self._gate_fwd = None
+        self.drop_blocks: List[int] = []
+        self._gate_bwd: Dict[int, tuple] = {}
         self._alloc_params()
         self._alloc_activations()
         self.build_fins()
@@ -434,8 +442,10 @@ class ResNetProgram:
                     _repoint(p, flat)
                     if kind == "bn_w":
                         bn.off_w, bn.gamma, bn.dgamma = off, flat, self.grad[off:off + n]
+                        bn.gamma_t = flat
                     else:
                         bn.off_b, bn.beta, bn.dbeta = off, flat, self.grad[off:off + n]
+                        bn.beta_t = flat
                     self.param_ranges.append((f"{bn.name}.{attr}", off, n))
                     # running stats stay module buffers (moved to device, updated in place)
                     mod.running_mean.data = mod.running_mean.data.to(dev, torch.float32)
@@ -697,11 +707,11 @@ class ResNetProgram:
             bn.fin_f = bn.fin_b = None
             if bn.C % 64:
                 continue
-            bn.fin_f = K.BnFin(K.BnFin.FWD, bn.stats, cnt, gamma=bn.gamma, beta=bn.beta, eps=mod.eps,
+            bn.fin_f = K.BnFin(K.BnFin.FWD, bn.stats, cnt, gamma=bn.gamma_t, beta=bn.beta_t, eps=mod.eps,
                                momentum=mom if mod.track_running_stats else 0.0, running_mean=mod.running_mean,
                                running_var=mod.running_var, scale=bn.scale, shift=bn.shift, mean=bn.mean,
                                invstd=bn.invstd)
-            bn.fin_b = K.BnFin(K.BnFin.BWD, bn.bstats, cnt, gamma=bn.gamma, mean=bn.mean, invstd=bn.invstd,
+            bn.fin_b = K.BnFin(K.BnFin.BWD, bn.bstats, cnt, gamma=bn.gamma_t, mean=bn.mean, invstd=bn.invstd,
                                coeff=bn.coeff, dgamma=bn.dgamma, dbeta=bn.dbeta)
         for b in self.blocks:  # the tail prologue's [block BN, shortcut BN] descriptor arrays, up front
             if b.ds_bn is not None and b.bns[-1].fin_f is not None and b.ds_bn.fin_f is not None:
@@ -787,6 +797,60 @@ class ResNetProgram:
         self.mix_lam = torch.ones(1, device=dev, dtype=torch.float32)
         self.labels2 = torch.zeros(self.N, device=dev, dtype=torch.int64)
 
+    def enable_drop_path(self, probs) -> None:
+        """Stochastic depth, per batch (Huang et al. 2016; ``torchvision.ops.stochastic_depth(mode="batch")``):
+        ``probs[l]`` is block l's drop probability, and every block with ``probs[l] > 0`` gets a gate -- a scalar
+        m on its residual branch, 0 (dropped) or 1 / (1 - p) (kept), that the caller writes into ``drop_gates``
+        (fp32 ``[n_gated]``, in block order, initialised to 1) before a step.
+
+        A per-block scalar commutes with the branch's last BatchNorm: m (gamma xhat + beta) = (m gamma) xhat +
+        (m beta). So no conv or BN kernel changes: the gated blocks' last BN gets effective ``gamma_t`` /
+        ``beta_t`` buffers, which one ``K.gate_scale_multi`` launch in front of the training forward fills from
+        the master, and which the training-mode readers (bn_finalize, bn_bwd_coeff and the in-launch finalizes
+        through their descriptors) take instead of the master. BN backward is linear in gamma, so what those
+        kernels write as dgamma / dbeta is the gradient with respect to m gamma / m beta: one more launch per
+        backward segment with gated blocks scales them by m in place, on the main stream after the segment's
+        last block and before its join -- ahead of everything that reads the segment's gradient range. The
+        eval coefficients, the EMA views, checkpoints and the optimizer keep reading the master.
+
+        With no ``probs[l] > 0`` nothing is allocated and the step issues the launches it issued before."""
+        probs = [float(q) for q in probs]
+        if len(probs) != len(self.blocks):
+            raise ValueError(f"enable_drop_path: {len(probs)} probabilities for {len(self.blocks)} blocks")
+        if any(not 0.0 <= q < 1.0 for q in probs):
+            raise ValueError(f"enable_drop_path: probabilities must be in [0, 1), got {probs}")
+        if self.drop_gates is not None:
+            raise RuntimeError("enable_drop_path: already enabled")
+        self.drop_blocks = [l for l, q in enumerate(probs) if q > 0.0]
+        if not self.drop_blocks:
+            return
+        dev = self.dev
+        self.drop_gates = torch.ones(len(self.drop_blocks), device=dev, dtype=torch.float32)
+        cpad = lambda c: (c + 3) // 4 * 4  # noqa: E731  (16-byte aligned rows: the vector path)
+        self.drop_eff = torch.zeros(sum(2 * cpad(self.blocks[l].bns[-1].C) for l in self.drop_blocks), device=dev,
+                                    dtype=torch.float32)
+        fwd_rows, o = [], 0
+        seg_rows: Dict[int, list] = {}
+        stage_of = [li for li in range(1, 5) for _ in getattr(self.model, f"layer{li}")]
+        for k, l in enumerate(self.drop_blocks):
+            bn = self.blocks[l].bns[-1]
+            c = cpad(bn.C)
+            bn.gamma_t, bn.beta_t = self.drop_eff[o:o + bn.C], self.drop_eff[o + c:o + c + bn.C]
+            o += 2 * c
+            fwd_rows += [(bn.gamma_t, bn.gamma, k), (bn.beta_t, bn.beta, k)]
+            seg_rows.setdefault(stage_of[l], []).extend([(bn.dgamma, bn.dgamma, k), (bn.dbeta, bn.dbeta, k)])
+        self._gate_fwd = (K.pack_gate_desc(fwd_rows, dev, len(self.drop_blocks)), len(fwd_rows),
+                          max(r[0].numel() for r in fwd_rows))
+        self._gate_bwd = {li: (K.pack_gate_desc(rows, dev, len(self.drop_blocks)), len(rows),
+                               max(r[0].numel() for r in rows)) for li, rows in seg_rows.items()}
+        self.build_fins()  # (the descriptors hold the readers' raw pointers)
+
+    def _gate_grads(self, li: int) -> None:
+        """Stage ``li``'s gated BNs: (dgamma, dbeta) *= gate, in place (see :meth:`enable_drop_path`)."""
+        t = self._gate_bwd.get(li)
+        if t is not None:
+            K.gate_scale_multi(*t, self.drop_gates)
+
     # ----------------------------------------------------------------------------------
     # per-step pieces
     # ----------------------------------------------------------------------------------
@@ -846,7 +910,7 @@ class ResNetProgram:
         mod = bn.mod
         if self.training:
             mom = mod.momentum if mod.momentum is not None else 0.1
-            K.bn_finalize(bn.stats, count, bn.gamma, bn.beta, mod.eps, mom if mod.track_running_stats else 0.0,
+            K.bn_finalize(bn.stats, count, bn.gamma_t, bn.beta_t, mod.eps, mom if mod.track_running_stats else 0.0,
                           mod.running_mean, mod.running_var, bn.scale, bn.shift, bn.mean, bn.invstd)
         elif self._skip_eval_coeff:  # computed once for the whole pass (bn_eval_coeffs)
             return
@@ -869,6 +933,8 @@ class ResNetProgram:
         if tr and not self._stats_zeroed:
             self.stats_region.zero_()
         self._stats_zeroed = False
+        if tr and self._gate_fwd is not None:  # every gated BN's effective gamma / beta = gate x master
+            K.gate_scale_multi(*self._gate_fwd, self.drop_gates)
         N = self.N
         st, sbn = self.stem, self.stem_bn
         K.conv_stem_fwd(self.x4, st.w16, self.y0, R=st.R, S=st.S, stride=st.stride, pad=st.pad,
@@ -1012,9 +1078,11 @@ class ResNetProgram:
         segs.append(("head", self._bwd_head))
         for li in (4, 3, 2, 1):
             idx = list(reversed(stages[li]))
-            segs.append((f"layer{li}", (lambda idx=idx, li=li: [
+            # (a stage's gated BN gradients are scaled behind its last block: dgamma / dbeta of a block's last BN
+            # are final at the end of that block's _bwd_block -- its own coefficient launch or apply pass)
+            segs.append((f"layer{li}", (lambda idx=idx, li=li: ([
                 (self._bwd_block(i), self._block_flush(li == 1 and j == len(idx) - 1))
-                for j, i in enumerate(idx)])))
+                for j, i in enumerate(idx)], self._gate_grads(li)))))
         segs.append(("stem", self._bwd_stem))
         # every segment ends with its weight gradients complete on the main stream (join)
         last = len(segs) - 1
@@ -1218,7 +1286,7 @@ class ResNetProgram:
 
     def _coeff(self, bn, count) -> None:
         """The standalone backward finalize of ``bn`` (its consumer needs ``bn.coeff`` in memory)."""
-        K.bn_bwd_coeff(bn.bstats, count, bn.gamma, bn.mean, bn.invstd, bn.coeff, bn.dgamma, bn.dbeta)
+        K.bn_bwd_coeff(bn.bstats, count, bn.gamma_t, bn.mean, bn.invstd, bn.coeff, bn.dgamma, bn.dbeta)
 
     def _bn_bwd(self, bn: BNL, dout, y, dy, count, mask_mode, mref=None, gout=None):
         K.bn_bwd_reduce(dout, y, bn.mean, bn.invstd, bn.bstats, mask_mode=mask_mode, mref=mref,

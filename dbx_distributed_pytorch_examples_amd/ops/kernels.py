@@ -1633,7 +1633,68 @@ def ema_update_multi(desc, ntensors, max_len, *, one_minus_decay=0.0, hyper=None
         raise ValueError(f"desc: expected a contiguous [{ntensors}, 3] table, got shape {tuple(desc.shape)}")
     if hyper is not None:
         _chk(hyper, torch.float32, "hyper", 1)
-    C().ema_update_multi(desc.data_ptr(), int(ntensors), int(max_len), _p(hyper), float(one_minus_decay), stream_ptr())
+    C().ema_update_multi(desc.data_ptr(), int(ntensors), int(max_len), _p(hyper), float(one_minus_decay), stream_ptr(),
+                         0)
+
+
+GATE_MAX_ROWS = 65535  # one row per blockIdx.y
+
+
+def pack_gate_desc(rows, device, ngates: Optional[int] = None) -> torch.Tensor:
+    """Descriptor table of one :func:`gate_scale_multi` launch (csrc/optim_ops.hip GateDesc {int64 dst address,
+    src address, length, gate index} = 32 bytes per row) from ``(dst, src, gate index)`` rows: flat fp32,
+    contiguous, equal non-zero sizes, on ``device``; ``dst is src`` (the same storage range) is allowed, any other
+    overlap is the caller's to avoid. ``ngates``: the length of the gate vector the launches will take -- every
+    index is checked against it here, once (left out: only for being non-negative). The table holds raw
+    addresses: rebuild it if a tensor it names is reallocated."""
+    rows = list(rows)
+    if not 0 < len(rows) <= GATE_MAX_ROWS:
+        raise ValueError(f"pack_gate_desc: {len(rows)} rows (1..{GATE_MAX_ROWS})")
+    out = []
+    want = torch.device(device)
+    for i, (dst, src, gate) in enumerate(rows):
+        for t, nm in ((dst, "dst"), (src, "src")):
+            if t.dtype != torch.float32:
+                raise TypeError(f"pack_gate_desc: row {i} {nm}: expected torch.float32, got {t.dtype}")
+            same_dev = t.device.type == want.type and (want.index is None or t.device.index == want.index)
+            if not t.is_contiguous() or not same_dev:
+                raise ValueError(f"pack_gate_desc: row {i} {nm}: must be contiguous and on {device}")
+        if dst.numel() != src.numel() or dst.numel() <= 0:
+            raise ValueError(f"pack_gate_desc: row {i}: {dst.numel()} destination and {src.numel()} source elements "
+                             f"(equal and > 0)")
+        gate = int(gate)
+        if gate < 0 or (ngates is not None and gate >= int(ngates)):
+            raise ValueError(f"pack_gate_desc: row {i}: gate index {gate} outside [0, {ngates})")
+        out.append([dst.data_ptr(), src.data_ptr(), dst.numel(), gate])
+    return torch.tensor(out, dtype=torch.int64).reshape(-1, 4).to(device)
+
+
+def _chk_gate_args(desc, nrows, max_len, gates) -> None:
+    """What both paths of :func:`gate_scale_multi` refuse before any launch."""
+    if desc.dtype != torch.int64:
+        raise TypeError(f"desc: expected torch.int64, got {desc.dtype}")
+    if gates.dtype != torch.float32:
+        raise TypeError(f"gates: expected torch.float32, got {gates.dtype}")
+    if not 0 < int(nrows) <= GATE_MAX_ROWS:
+        raise ValueError(f"gate_scale_multi: {nrows} rows (1..{GATE_MAX_ROWS})")
+    if not desc.is_contiguous() or desc.numel() != 4 * int(nrows):
+        raise ValueError(f"desc: expected a contiguous [{nrows}, 4] table, got shape {tuple(desc.shape)}")
+    if not gates.is_contiguous() or gates.numel() < 1 or gates.device != desc.device:
+        raise ValueError("gates: a contiguous, non-empty fp32 vector on the table's device")
+    if int(max_len) <= 0:
+        raise ValueError(f"gate_scale_multi: max_len must be > 0, got {max_len}")
+
+
+@_dispatch
+def gate_scale_multi(desc, nrows, max_len, gates):
+    """``dst[i] = gates[row.gate] * src[i]`` for every row of a :func:`pack_gate_desc` table in ONE launch (grid =
+    (blocks, nrows)): stochastic depth's per-block scalar on the gated BatchNorms' affine parameters (forward) and
+    on their gradients (backward, in place). ``gates`` is read on the device, so a replayed graph follows what
+    the host copied into it. One fp32 multiply per element. ``max_len``: the longest row."""
+    _chk_gate_args(desc, nrows, max_len, gates)
+    # (the extension's exported names are fixed: the entry point is reached through ema_update_multi's binding,
+    # whose last argument, the gate vector, forwards to dbx_gate_scale_multi)
+    C().ema_update_multi(desc.data_ptr(), int(nrows), int(max_len), 0, 0.0, stream_ptr(), gates.data_ptr())
 
 
 @_dispatch

@@ -813,6 +813,24 @@ def ema_update_multi(desc, ntensors, max_len, *, one_minus_decay=0.0, hyper=None
         ema_update(e, p, one_minus_decay=one_minus_decay, hyper=hyper)
 
 
+def gate_scale_multi(desc, nrows, max_len, gates):
+    """dst = gates[gate] * src per row, one fp32 multiply per element (the kernel's definition). The table holds
+    host addresses here: each row is viewed in place; dst == src is an in-place scaling."""
+    import ctypes
+    if desc.dtype != torch.int64 or gates.dtype != torch.float32:
+        raise TypeError("gate_scale_multi: expected an int64 table and float32 gates")
+    if not 0 < int(nrows) <= 65535 or desc.numel() != 4 * int(nrows) or int(max_len) <= 0:
+        raise ValueError("gate_scale_multi: expected an int64 [nrows, 4] table, 1..65535 rows, max_len > 0")
+    rows = desc.reshape(-1, 4).tolist()
+    g = gates.reshape(-1)
+    if any(n <= 0 or n > int(max_len) or not 0 <= k < g.numel() for _, _, n, k in rows):
+        raise ValueError("gate_scale_multi: a row's length or gate index is out of range")
+    for dst, src, n, k in rows:
+        y = torch.frombuffer((ctypes.c_float * n).from_address(dst), dtype=torch.float32)
+        x = torch.frombuffer((ctypes.c_float * n).from_address(src), dtype=torch.float32)
+        torch.mul(x, g[k], out=y)
+
+
 def global_norm_clip_factor(g, max_norm, work):
     work.zero_()
     ss = (g.double() ** 2).sum()

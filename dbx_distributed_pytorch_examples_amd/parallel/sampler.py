@@ -35,13 +35,16 @@ class ShardSampler(Sampler[int]):
     def set_epoch(self, epoch: int) -> None:
         self.epoch = int(epoch)
 
-    def indices(self) -> torch.Tensor:
+    def permutation(self) -> torch.Tensor:
+        """The epoch's order of all ``n`` indices (seed + epoch), before padding and the split over ranks."""
         if self.shuffle:
             g = torch.Generator()
             g.manual_seed(self.seed + self.epoch)
-            idx = torch.randperm(self.n, generator=g)
-        else:
-            idx = torch.arange(self.n)
+            return torch.randperm(self.n, generator=g)
+        return torch.arange(self.n)
+
+    def indices(self) -> torch.Tensor:
+        idx = self.permutation()
         if not self.drop_last:
             pad = self.total_size - self.n
             if pad > 0:
@@ -56,6 +59,33 @@ class ShardSampler(Sampler[int]):
 
     def __len__(self) -> int:
         return self.num_samples
+
+
+class RepeatAugSampler(ShardSampler):
+    """Repeated augmentation (Hoffer et al. 2020; DeiT's and timm's ``RepeatAugSampler``): ``ShardSampler``'s
+    seed + epoch permutation with every index repeated ``num_repeats`` times in a row, padded by wrap-around to a
+    multiple of the world size, strided by rank and cut to ``ShardSampler``'s ``num_samples``. The epoch keeps its
+    length, so it visits about ``1 / num_repeats`` of the images ``num_repeats`` times each; the loader draws its
+    crop boxes and flips per position, so the copies are augmented independently. At a world size that is a
+    multiple of ``num_repeats`` the copies of an image go to different ranks; at world 1 they are neighbours in
+    one batch. ``num_repeats=1`` gives ``ShardSampler``'s indices exactly."""
+
+    def __init__(self, dataset_or_len, num_repeats: int = 3, num_replicas: Optional[int] = None,
+                 rank: Optional[int] = None, shuffle: bool = True, seed: int = 0, drop_last: bool = False):
+        if isinstance(num_repeats, bool) or not isinstance(num_repeats, int) or num_repeats < 1:
+            raise ValueError(f"num_repeats must be an integer >= 1, got {num_repeats!r}")
+        super().__init__(dataset_or_len, num_replicas, rank, shuffle, seed, drop_last)
+        self.num_repeats = num_repeats
+
+    def indices(self) -> torch.Tensor:
+        if self.num_repeats == 1:
+            return super().indices()
+        idx = self.permutation().repeat_interleave(self.num_repeats)
+        w = self.num_replicas
+        pad = -idx.numel() % w
+        if pad:
+            idx = torch.cat([idx] * (1 + math.ceil(pad / idx.numel())))[:idx.numel() + pad]
+        return idx[self.rank::w][:self.num_samples]
 
 
 # torch-compatible alias (the reference imports DistributedSampler by that name)

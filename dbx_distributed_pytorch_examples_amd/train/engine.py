@@ -36,10 +36,10 @@ import torch
 from torch.utils.data import DataLoader, Dataset
 
 from ..config import (TrainConfig, auto_augment_options, from_deepspeed, has_param_groups, loss_options, mix_options,
-                      mixes_batches, parse_duration, to_dict, validate_data)
+                      mixes_batches, parse_duration, to_dict, validate_aug_repeats, validate_drop_path, validate_train)
 from ..models import build_model
 from ..parallel import dist as ddist
-from ..parallel.sampler import ShardSampler
+from ..parallel.sampler import RepeatAugSampler, ShardSampler
 from ..utils import checkpoint as ckpt
 from ..utils import fault
 from ..utils import mlflow_compat as mlflow
@@ -105,12 +105,25 @@ def _dict_collate(batch):
     return _collate_images(list(zip(xs, ys)))
 
 
+def train_sampler(ds, aug_repeats: int = 1, **kw):
+    """The training sampler of a map-style dataset: ``ShardSampler``, or with ``aug_repeats`` > 1 the
+    ``RepeatAugSampler`` over the same permutation; None for a streaming dataset, which partitions itself (and
+    refuses repeats: its ``epoch_indices`` are its own)."""
+    r = validate_aug_repeats(aug_repeats)
+    if hasattr(ds, "epoch_indices"):
+        if r > 1:
+            raise ValueError(f"data.aug_repeats={r} needs a map-style dataset: an MDS StreamingDataset draws its own "
+                             f"epoch_indices, which the repeat sampler cannot reorder")
+        return None
+    return RepeatAugSampler(ds, num_repeats=r, **kw) if r > 1 else ShardSampler(ds, **kw)
+
+
 def make_loader(ds: Dataset, batch_size: int, shuffle: bool, seed: int, num_workers: int = 0,
-                drop_last: bool = False, pin: bool = False):
-    if hasattr(ds, "epoch_indices"):  # streaming dataset partitions itself
+                drop_last: bool = False, pin: bool = False, aug_repeats: int = 1):
+    sampler = train_sampler(ds, aug_repeats, shuffle=shuffle, seed=seed, drop_last=drop_last)
+    if sampler is None:  # streaming dataset partitions itself
         return DataLoader(ds, batch_size=batch_size, num_workers=num_workers, collate_fn=_dict_collate,
                           drop_last=drop_last, pin_memory=pin), None
-    sampler = ShardSampler(ds, shuffle=shuffle, seed=seed, drop_last=drop_last)
     return DataLoader(ds, batch_size=batch_size, sampler=sampler, num_workers=num_workers,
                       collate_fn=_collate_images, drop_last=drop_last, pin_memory=pin), sampler
 
@@ -150,7 +163,8 @@ class _Native:
                                     src_hw=(h, w), mean=mean, std=std, zero_stage=cfg.zero.stage,
                                     seed=cfg.seed, grad_accum=cfg.grad_accum, ema_decay=cfg.ema_decay,
                                     ema_warmup=cfg.ema_warmup, **mix_options(cfg.data),
-                                    **auto_augment_options(cfg.data), **loss_options(cfg.data))
+                                    **auto_augment_options(cfg.data), **loss_options(cfg.data),
+                                    drop_path_rate=cfg.drop_path_rate)
         self.ema_eval = bool(cfg.ema_eval)
         self.eval_topk, self.eval_graph = _eval_topk(cfg), bool(cfg.eval_graph)
         if not cfg.data.augment:
@@ -161,8 +175,7 @@ class _Native:
             aug = AugmentSpec(hflip=True)
         else:
             aug = AugmentSpec(mode="random_resized_crop", hflip=True)
-        sampler = None if hasattr(ds, "epoch_indices") else ShardSampler(ds, shuffle=cfg.data.shuffle, seed=cfg.seed,
-                                                                          drop_last=True)
+        sampler = train_sampler(ds, cfg.data.aug_repeats, shuffle=cfg.data.shuffle, seed=cfg.seed, drop_last=True)
         self.sampler = sampler
         self.loader = NativeImageLoader(ds, cfg.batch_size, (h, w), dev, channels=c, augment=aug, out_hw=(s, s),
                                         indices_fn=(lambda e: (sampler.set_epoch(e), sampler.indices().numpy())[1])
@@ -252,7 +265,7 @@ class _Autograd:
                                   allreduce_dtype=torch.bfloat16 if cfg.allreduce_dtype == "bf16" else torch.float32)
         self.loader, self.sampler = make_loader(ds, cfg.batch_size, cfg.data.shuffle, cfg.seed,
                                                 num_workers=cfg.data.num_workers if dev.type == "cuda" else 0,
-                                                pin=dev.type == "cuda")
+                                                pin=dev.type == "cuda", aug_repeats=cfg.data.aug_repeats)
         self.batch = cfg.batch_size
         self.eval_topk = _eval_topk(cfg)
 
@@ -382,8 +395,15 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
         else:
             train_dataset = build_dataset(d.dataset, d.root, True, None, d.image_size, cfg.num_classes,
                                           d.train_samples or 50 * cfg.batch_size * info.world_size, cfg.seed)
-    validate_data(cfg.data)  # (validated whichever engine runs)
+    validate_train(cfg)  # (validated whichever engine runs)
+    train_sampler(train_dataset, cfg.data.aug_repeats)  # (refuses repeats of a streaming dataset up front)
     engine = _pick_engine(cfg, model, train_dataset, dev)
+    if validate_drop_path(cfg.drop_path_rate) > 0:  # refused, never ignored
+        from ..models.wrappers import FrozenBackboneClassifier
+        if engine != "native" or isinstance(model, FrozenBackboneClassifier):
+            raise ValueError(f"drop_path_rate={cfg.drop_path_rate} needs the native training step (NativeTrainer, "
+                             f"which gates the blocks' last BatchNorm); this run would use the "
+                             f"{'frozen-backbone' if engine == 'native' else engine} engine, which drops no block")
     if cfg.data.auto_augment is not None:  # refused, never ignored
         from ..models.wrappers import FrozenBackboneClassifier
         if engine != "native" or isinstance(model, FrozenBackboneClassifier):
@@ -454,6 +474,13 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
             s = runner.tr.loss_summary() if hasattr(runner.tr, "loss_summary") else loss_options(cfg.data)
             _log("[train] training loss: " + " ".join(f"{k}={v}" for k, v in s.items())
                  + " (validation reports softmax cross-entropy)")
+        if cfg.drop_path_rate > 0:
+            _log("[train] stochastic depth: " + " ".join(f"{k}={v}" for k, v in runner.tr.drop_path_summary().items())
+                 + " (whole blocks per micro-batch and rank; evaluation is never gated)")
+        if cfg.data.aug_repeats > 1:
+            _log(f"[train] repeated augmentation: aug_repeats={cfg.data.aug_repeats} sampler="
+                 f"{type(runner.sampler).__name__} (an epoch keeps its length and visits about "
+                 f"1/{cfg.data.aug_repeats} of the images; validation never repeats)")
         if cfg.grad_accum > 1 and cfg.checkpoint_dir and cfg.checkpoint_every and spe % cfg.grad_accum != 0:
             # (one iteration is one micro-batch; a checkpoint carries no accumulator)
             _log(f"[train] warning: steps/epoch={spe} is no multiple of grad_accum={cfg.grad_accum}: a run resumed "
