@@ -145,6 +145,33 @@ class DataConfig:
     # times in a row in the epoch's order, each copy augmented on its own; the epoch keeps its length, so it visits
     # about 1 / aug_repeats of the images. Map-style datasets only; validation never repeats.
     aug_repeats: int = 1
+    # ragged input batches (native engine): the images keep the sizes they were written with, up to ragged_max_hw
+    # (height, width); a batch is one byte arena and a table, and the GPU crops every sample from its own geometry
+    # (RandomResizedCrop draws on the original image). ragged_oversize: error | crop (cut around the centre).
+    ragged: bool = False
+    ragged_max_hw: Tuple[int, int] = (512, 512)
+    ragged_oversize: str = "error"
+
+
+RAGGED_OVERSIZE = ("error", "crop")
+
+
+def ragged_options(d: DataConfig) -> Dict[str, Any]:
+    """The loader's ``ragged_max_hw`` / ``oversize`` from ``cfg.data``, validated; ``{}`` while ``ragged`` is off
+    (ValueError: a ``ragged_*`` option away from its default then -- refused, never ignored)."""
+    if not isinstance(d.ragged, bool):
+        raise ValueError(f"data.ragged must be a bool, got {d.ragged!r}")
+    hw = tuple(d.ragged_max_hw) if isinstance(d.ragged_max_hw, (list, tuple)) else d.ragged_max_hw
+    if (not isinstance(hw, tuple) or len(hw) != 2
+            or any(isinstance(v, bool) or not isinstance(v, int) or v < 1 for v in hw)):
+        raise ValueError(f"data.ragged_max_hw must be two integers >= 1 (height, width), got {d.ragged_max_hw!r}")
+    if d.ragged_oversize not in RAGGED_OVERSIZE:
+        raise ValueError(f"data.ragged_oversize must be one of {RAGGED_OVERSIZE}, got {d.ragged_oversize!r}")
+    if not d.ragged:
+        if hw != (512, 512) or d.ragged_oversize != "error":
+            raise ValueError("data.ragged_max_hw / data.ragged_oversize need data.ragged: true")
+        return {}
+    return dict(ragged_max_hw=hw, oversize=d.ragged_oversize)
 
 
 def mix_options(d: DataConfig) -> Dict[str, Any]:
@@ -215,6 +242,7 @@ def validate_data(d: DataConfig) -> None:
     auto_augment_options(d)
     loss_options(d)
     validate_aug_repeats(d.aug_repeats)
+    ragged_options(d)
 
 
 def validate_drop_path(rate: Any) -> float:

@@ -102,19 +102,25 @@ int dbx_sumsq(const float* x, long long n, double* out, hipStream_t st);
 int dbx_clip_factor(const double* sumsq, float max_norm, float* out, hipStream_t st);
 
 // ---- input pipeline (input_ops.hip) -----------------------------------------------------------------------------
+// augment_u8, augment_mix_u8 and crop_resize_u8 read a dense batch [N][Hin][Win][Cin], or -- with src_tab, an int32
+// [N][4] table (offset / 16, H, W, stride) -- images of different sizes packed in the byte arena `in` of arena16
+// 16-byte units (Hin / Win are then unread)
 int dbx_normalize_u8(const unsigned char* in, bf16* out, const unsigned char* flip, int N, int H, int W, int Cin,
                      float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st);
 int dbx_augment_u8(const unsigned char* in, bf16* out, const float* boxes, const unsigned char* flip, int N, int Hin,
                    int Win, int Cin, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1, float s2,
-                   const int* perm, const int* mixbox, hipStream_t st);
+                   const int* perm, const int* mixbox, hipStream_t st, const int* src_tab = nullptr,
+                   long long arena16 = 0);
 // the augment kernel with a MixUp blend and / or random erasing
 int dbx_augment_mix_u8(const unsigned char* in, bf16* out, const float* boxes, const unsigned char* flip, int N,
                        int Hin, int Win, int Cin, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1,
                        float s2, const int* perm, const int* mixbox, const float* blend, const int* erase, int pixel,
-                       unsigned long long seed, const int* rng_offset, hipStream_t st);
+                       unsigned long long seed, const int* rng_offset, hipStream_t st, const int* src_tab = nullptr,
+                       long long arena16 = 0);
 // TrivialAugmentWide: source uint8 -> T (R, G, B, L) + histograms; LUTs and gray means; the mixing kernel on T
 int dbx_crop_resize_u8(const unsigned char* in, unsigned char* T, int* hist, const float* boxes,
-                       const unsigned char* flip, int N, int Hin, int Win, int Ho, int Wo, hipStream_t st);
+                       const unsigned char* flip, int N, int Hin, int Win, int Ho, int Wo, hipStream_t st,
+                       const int* src_tab = nullptr, long long arena16 = 0);
 int dbx_ta_prepare(const int* hist, const int* ops, unsigned char* lut, int* tmean, int N, hipStream_t st);
 int dbx_ta_apply_u8(const unsigned char* T, bf16* out, const int* ops, const unsigned char* lut, const int* tmean,
                     int N, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1, float s2, const int* perm,

@@ -78,43 +78,95 @@ __device__ __forceinline__ AugBox aug_box(const float* __restrict__ boxes, const
                                           int Wo) {
   return AugBox{sn, boxes[4 * sn], boxes[4 * sn + 1], boxes[4 * sn + 2], boxes[4 * sn + 3] / Wo, flip && flip[sn]};
 }
+// One source image: where its rows are, its size and the bytes from one row to the next. Dense batch
+// [N][Hin][Win][Cin]: sample sn of it (base = the batch, rows sn Hin + y: the addressing these kernels always had). Ragged batch: a byte arena of `arena16` 16-byte units and the table tab int32 [N][4] =
+// (offset / 16, H, W, stride) (data/loader.py pack_layout: stride = ceil16(W Cin), offsets the running sum of
+// H stride, so every row starts 16-byte aligned and a row of at most kRowMax bytes can be staged). A table row is
+// unusable when its extent leaves the arena, H < 1, W < 1, stride < W Cin or stride % 16 != 0; it is then read as
+// the row (0, 1, 1, 16) -- the arena's first pixel -- and never dereferenced (base = the image, sn = 0).
+// Block-uniform either way.
+struct SrcImg {
+  const unsigned char* base;
+  int sn, H, W, rb;
+};
+template <bool RAGGED>
+__device__ __forceinline__ SrcImg src_img(const unsigned char* __restrict__ in, const int* __restrict__ tab,
+                                          long long arena16, int sn, int Hin, int Win, int Cin) {
+  if constexpr (!RAGGED) {
+    return SrcImg{in, sn, Hin, Win, Win * Cin};
+  } else {
+    const long long off = tab[4 * sn];
+    const int H = tab[4 * sn + 1], W = tab[4 * sn + 2], rb = tab[4 * sn + 3];
+    const bool ok = off >= 0 && H >= 1 && W >= 1 && (rb & 15) == 0 && (long long)rb >= (long long)W * Cin &&
+                    off + (((long long)H * rb) >> 4) <= arena16;
+    return ok ? SrcImg{in + (size_t)off * 16, 0, H, W, rb} : SrcImg{in, 0, 1, 1, 16};
+  }
+}
+
 struct AugRow {
   const unsigned char *g0, *g1;
   float bx, sxs, wy;
+  int W, rb;  // the source's width and the bytes of a row of it
   bool fl;
   MixSrc src;
 };
 // `erase`: the erase table of the mixing form, else null
-__device__ __forceinline__ AugRow aug_row(const unsigned char* __restrict__ in, const AugBox& b,
-                                          const int* __restrict__ erase, int oy, int Hin, int Win, int Cin, int Ho) {
+template <bool RAGGED>
+__device__ __forceinline__ AugRow aug_row(const SrcImg& im, const AugBox& b, const int* __restrict__ erase, int oy,
+                                          int Cin, int Ho) {
   AugRow r;
-  const int sn = b.sn;
   r.bx = b.bx;
   r.fl = b.fl;
   float sy = b.by + (oy + 0.5f) * b.bh / Ho - 0.5f;
-  sy = fminf(fmaxf(sy, 0.f), (float)(Hin - 1));
-  const int y0 = (int)sy, y1 = min(y0 + 1, Hin - 1);
+  sy = fminf(fmaxf(sy, 0.f), (float)(im.H - 1));
+  const int y0 = (int)sy, y1 = min(y0 + 1, im.H - 1);
   r.wy = sy - y0;
-  r.g0 = in + ((size_t)sn * Hin + y0) * Win * Cin;
-  r.g1 = in + ((size_t)sn * Hin + y1) * Win * Cin;
+  if constexpr (RAGGED) {
+    r.g0 = im.base + (size_t)y0 * im.rb;
+    r.g1 = im.base + (size_t)y1 * im.rb;
+  } else {
+    r.g0 = im.base + ((size_t)im.sn * im.H + y0) * im.W * Cin;
+    r.g1 = im.base + ((size_t)im.sn * im.H + y1) * im.W * Cin;
+  }
+  r.W = im.W;
+  r.rb = im.rb;
   r.sxs = b.sxs;
-  r.src = mix_src(erase, sn, oy);
+  r.src = mix_src(erase, b.sn, oy);
   return r;
 }
 
-// Stages A's two rows of rb bytes in srow[0..1] (and, with `two`, P's in srow[2..3]) when all can be: they fit
-// and the 16-byte loads are aligned. Block-uniform; false: the caller gathers from global memory.
-__device__ __forceinline__ bool stage_rows(unsigned char (*srow)[kRowMax], int rb, const AugRow& A, const AugRow& P,
-                                           bool two) {
-  const bool staged = rb <= kRowMax && (rb & 15) == 0 &&
-                      (((size_t)A.g0 | (size_t)A.g1 | (size_t)P.g0 | (size_t)P.g1) & 15) == 0;
+// Stages A's two rows of A.rb bytes in srow[0..1] (and, with `two`, P's of P.rb bytes in srow[2..3]) when all can
+// be: they fit and the 16-byte loads are aligned. Block-uniform; false: the caller gathers from global memory.
+// Dense: both sources have the batch's row bytes. Ragged: each its own (a multiple of 16 by the table's guard).
+template <bool RAGGED>
+__device__ __forceinline__ bool stage_rows(unsigned char (*srow)[kRowMax], const AugRow& A, const AugRow& P, bool two) {
+  const int rb = A.rb;
+  bool staged = rb <= kRowMax && (rb & 15) == 0 &&
+                (((size_t)A.g0 | (size_t)A.g1 | (size_t)P.g0 | (size_t)P.g1) & 15) == 0;
+  if constexpr (RAGGED) staged = staged && P.rb <= kRowMax && (P.rb & 15) == 0;
   if (staged) {
-    for (int o = threadIdx.x * 16; o < rb; o += blockDim.x * 16) {
-      *reinterpret_cast<u32x4*>(&srow[0][o]) = *reinterpret_cast<const u32x4*>(A.g0 + o);
-      *reinterpret_cast<u32x4*>(&srow[1][o]) = *reinterpret_cast<const u32x4*>(A.g1 + o);
-      if (two) {
-        *reinterpret_cast<u32x4*>(&srow[2][o]) = *reinterpret_cast<const u32x4*>(P.g0 + o);
-        *reinterpret_cast<u32x4*>(&srow[3][o]) = *reinterpret_cast<const u32x4*>(P.g1 + o);
+    if constexpr (!RAGGED) {
+      for (int o = threadIdx.x * 16; o < rb; o += blockDim.x * 16) {
+        *reinterpret_cast<u32x4*>(&srow[0][o]) = *reinterpret_cast<const u32x4*>(A.g0 + o);
+        *reinterpret_cast<u32x4*>(&srow[1][o]) = *reinterpret_cast<const u32x4*>(A.g1 + o);
+        if (two) {
+          *reinterpret_cast<u32x4*>(&srow[2][o]) = *reinterpret_cast<const u32x4*>(P.g0 + o);
+          *reinterpret_cast<u32x4*>(&srow[3][o]) = *reinterpret_cast<const u32x4*>(P.g1 + o);
+        }
+      }
+    } else {
+      // one loop over the longer row, all four loads of a thread in flight together as in the dense form: past the
+      // end of the shorter row the offset is clamped to its last 16 bytes (rb >= 16), which are staged again with
+      // the same bytes
+      const int rbp = two ? P.rb : rb, rbm = max(rb, rbp);
+      for (int o = threadIdx.x * 16; o < rbm; o += blockDim.x * 16) {
+        const int oa = min(o, rb - 16), op = min(o, rbp - 16);
+        *reinterpret_cast<u32x4*>(&srow[0][oa]) = *reinterpret_cast<const u32x4*>(A.g0 + oa);
+        *reinterpret_cast<u32x4*>(&srow[1][oa]) = *reinterpret_cast<const u32x4*>(A.g1 + oa);
+        if (two) {
+          *reinterpret_cast<u32x4*>(&srow[2][op]) = *reinterpret_cast<const u32x4*>(P.g0 + op);
+          *reinterpret_cast<u32x4*>(&srow[3][op]) = *reinterpret_cast<const u32x4*>(P.g1 + op);
+        }
       }
     }
     __syncthreads();
@@ -126,11 +178,11 @@ __device__ __forceinline__ bool stage_rows(unsigned char (*srow)[kRowMax], int r
 // by channel (crop_resize_u8 rounds each value where it is made); below, all three into v[]
 template <typename Each>
 __device__ __forceinline__ void bilinear(const AugRow& r, const unsigned char* r0, const unsigned char* r1, int ox,
-                                         int Win, int Cin, int Wo, Each each) {
+                                         int Cin, int Wo, Each each) {
   const int oxx = r.fl ? (Wo - 1 - ox) : ox;
   float sx = r.bx + (oxx + 0.5f) * r.sxs - 0.5f;
-  sx = fminf(fmaxf(sx, 0.f), (float)(Win - 1));
-  const int x0 = (int)sx, x1 = min(x0 + 1, Win - 1);
+  sx = fminf(fmaxf(sx, 0.f), (float)(r.W - 1));
+  const int x0 = (int)sx, x1 = min(x0 + 1, r.W - 1);
   const float wx = sx - x0, wy = r.wy;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -141,8 +193,8 @@ __device__ __forceinline__ void bilinear(const AugRow& r, const unsigned char* r
   }
 }
 __device__ __forceinline__ void bilinear(const AugRow& r, const unsigned char* r0, const unsigned char* r1, int ox,
-                                         int Win, int Cin, int Wo, float (&v)[3]) {
-  bilinear(r, r0, r1, ox, Win, Cin, Wo, [&](int c, float x) __attribute__((always_inline)) { v[c] = x; });
+                                         int Cin, int Wo, float (&v)[3]) {
+  bilinear(r, r0, r1, ox, Cin, Wo, [&](int c, float x) __attribute__((always_inline)) { v[c] = x; });
 }
 
 // ----------------------------------------------------------------------------------------
@@ -261,13 +313,17 @@ __global__ void normalize_u8_kernel(const unsigned char* __restrict__ in, bf16* 
 // `03_composer/01_cifar_composer_resnet.ipynb:430`): with perm / mixbox set, output pixels inside the box come
 // from sample perm[n] -- sampled with ITS crop box and flip, i.e. exactly the pixels of the augmented image
 // perm[n] at the same output position.
+// RAGGED (this kernel, the mixing form and crop_resize_u8): `in` is the arena and every source sample has its own
+// geometry in `tab` (src_img above; Hin / Win are unread); the dense instantiation never reads tab / arena16.
 // ----------------------------------------------------------------------------------------
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void augment_u8_kernel(const unsigned char* __restrict__ in, bf16* __restrict__ out,
                                                          const float* __restrict__ boxes,
                                                          const unsigned char* __restrict__ flip, int N, int Hin,
                                                          int Win, int Cin, int Ho, int Wo, float m0, float m1,
                                                          float m2, float s0, float s1, float s2,
-                                                         const int* __restrict__ perm, const int* __restrict__ mixbox) {
+                                                         const int* __restrict__ perm, const int* __restrict__ mixbox,
+                                                         const int* __restrict__ tab, long long arena16) {
   __shared__ __attribute__((aligned(16))) unsigned char srow[2][kRowMax];
   const MixBox box = mix_box(mixbox);
   const Norm nm = make_norm(m0, m1, m2, s0, s1, s2);
@@ -277,13 +333,15 @@ __global__ __launch_bounds__(256) void augment_u8_kernel(const unsigned char* __
     // pass 0: sample n outside the box (everywhere when not mixing); pass 1: sample perm[n] inside
     for (int pass = 0; pass < (mixrow ? 2 : 1); ++pass) {
       const int xlo = pass ? box.x0 : 0, xhi = pass ? box.x1 : Wo;
-      const AugRow r = aug_row(in, aug_box(boxes, flip, pass ? perm[n] : n, Wo), nullptr, oy, Hin, Win, Cin, Ho);
-      const bool staged = stage_rows(srow, Win * Cin, r, r, false);
+      const int sn = pass ? perm[n] : n;
+      const AugRow r = aug_row<RAGGED>(src_img<RAGGED>(in, tab, arena16, sn, Hin, Win, Cin),
+                                       aug_box(boxes, flip, sn, Wo), nullptr, oy, Cin, Ho);
+      const bool staged = stage_rows<RAGGED>(srow, r, r, false);
       auto body = [&](const unsigned char* r0, const unsigned char* r1) __attribute__((always_inline)) {
         for (int ox = xlo + threadIdx.x; ox < xhi; ox += blockDim.x) {
           if (mixrow && !pass && ox >= box.x0 && ox < box.x1) continue;  // pasted by pass 1
           float v[3], f[3];
-          bilinear(r, r0, r1, ox, Win, Cin, Wo, v);
+          bilinear(r, r0, r1, ox, Cin, Wo, v);
           normalise(nm, v, f);
           store_px(out, row, Wo, ox, f);
         }
@@ -296,27 +354,32 @@ __global__ __launch_bounds__(256) void augment_u8_kernel(const unsigned char* __
 }
 
 // The mixing form: a row stages the two source rows of both samples (4 x 4096 B of LDS) when all four can be.
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void augment_mix_u8_kernel(const unsigned char* __restrict__ in, bf16* __restrict__ out,
                                                              const float* __restrict__ boxes,
                                                              const unsigned char* __restrict__ flip, int N, int Hin,
                                                              int Win, int Cin, int Ho, int Wo, float m0, float m1,
                                                              float m2, float s0, float s1, float s2,
                                                              const int* __restrict__ perm,
-                                                             const int* __restrict__ mixbox, const AugMix am) {
+                                                             const int* __restrict__ mixbox, const AugMix am,
+                                                             const int* __restrict__ tab, long long arena16) {
   __shared__ __attribute__((aligned(16))) unsigned char srow[4][kRowMax];
   const Mix mix = make_mix(perm, mixbox, am);
   const Norm nm = make_norm(m0, m1, m2, s0, s1, s2);
   for (int row = blockIdx.x; row < N * Ho; row += gridDim.x) {  // row = n * Ho + oy
     const int n = row / Ho, oy = row - n * Ho;
     const MixRow R = mix_row(mix, perm, n, oy, N);
-    const AugRow A = aug_row(in, aug_box(boxes, flip, n, Wo), am.erase, oy, Hin, Win, Cin, Ho);
-    const AugRow P = R.two ? aug_row(in, aug_box(boxes, flip, R.other, Wo), am.erase, oy, Hin, Win, Cin, Ho) : A;
-    const bool staged = stage_rows(srow, Win * Cin, A, P, R.two);
+    const AugRow A = aug_row<RAGGED>(src_img<RAGGED>(in, tab, arena16, n, Hin, Win, Cin), aug_box(boxes, flip, n, Wo),
+                                     am.erase, oy, Cin, Ho);
+    const AugRow P = R.two ? aug_row<RAGGED>(src_img<RAGGED>(in, tab, arena16, R.other, Hin, Win, Cin),
+                                             aug_box(boxes, flip, R.other, Wo), am.erase, oy, Cin, Ho)
+                           : A;
+    const bool staged = stage_rows<RAGGED>(srow, A, P, R.two);
     auto body = [&](const unsigned char* a0, const unsigned char* a1, const unsigned char* p0, const unsigned char* p1)
                     __attribute__((always_inline)) {
       auto px = [&](int k, int ox, float (&f)[3]) __attribute__((always_inline)) {
         float v[3];
-        bilinear(k ? P : A, k ? p0 : a0, k ? p1 : a1, ox, Win, Cin, Wo, v);
+        bilinear(k ? P : A, k ? p0 : a0, k ? p1 : a1, ox, Cin, Wo, v);
         normalise(nm, v, f);
       };
       mix_columns(mix, R, am, A.src, P.src, out, row, oy, Ho, Wo, 0, Wo, px);
@@ -346,11 +409,13 @@ __global__ __launch_bounds__(256) void augment_mix_u8_kernel(const unsigned char
 // ----------------------------------------------------------------------------------------
 // crop_resize_u8: a block takes kTaRows consecutive output rows of one sample (one LDS histogram flush per
 // chunk, not per row).
+template <bool RAGGED>
 __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const unsigned char* __restrict__ in,
                                                              unsigned* __restrict__ T, int* __restrict__ hist,
                                                              const float* __restrict__ boxes,
                                                              const unsigned char* __restrict__ flip, int N, int Hin,
-                                                             int Win, int Ho, int Wo) {
+                                                             int Win, int Ho, int Wo, const int* __restrict__ tab,
+                                                             long long arena16) {
   constexpr int Cin = 3;
   __shared__ __attribute__((aligned(16))) unsigned char srow[2][kRowMax];
   __shared__ int sh[4 * 256];
@@ -359,14 +424,15 @@ __global__ __launch_bounds__(256) void crop_resize_u8_kernel(const unsigned char
     const int n = chunk / cps, r0 = (chunk - n * cps) * kTaRows, r1 = min(r0 + kTaRows, Ho);
     for (int i = threadIdx.x; i < 4 * 256; i += blockDim.x) sh[i] = 0;
     const AugBox b = aug_box(boxes, flip, n, Wo);
+    const SrcImg im = src_img<RAGGED>(in, tab, arena16, n, Hin, Win, Cin);
     __syncthreads();
     for (int oy = r0; oy < r1; ++oy) {
-      const AugRow r = aug_row(in, b, nullptr, oy, Hin, Win, Cin, Ho);
-      const bool staged = stage_rows(srow, Win * Cin, r, r, false);
+      const AugRow r = aug_row<RAGGED>(im, b, nullptr, oy, Cin, Ho);
+      const bool staged = stage_rows<RAGGED>(srow, r, r, false);
       auto body = [&](const unsigned char* r0p, const unsigned char* r1p) __attribute__((always_inline)) {
         for (int ox = threadIdx.x; ox < Wo; ox += blockDim.x) {
           int u[3];
-          bilinear(r, r0p, r1p, ox, Win, Cin, Wo,
+          bilinear(r, r0p, r1p, ox, Cin, Wo,
                    [&](int c, float v) __attribute__((always_inline)) { u[c] = min(max((int)(v + 0.5f), 0), 255); });
           const int L = (19595 * u[0] + 38470 * u[1] + 7471 * u[2] + 0x8000) >> 16;  // <= 255
           T[((size_t)n * Ho + oy) * Wo + ox] = (unsigned)u[0] | ((unsigned)u[1] << 8) | ((unsigned)u[2] << 16) |
@@ -653,25 +719,40 @@ extern "C" int dbx_normalize_u8(const unsigned char* in, bf16* out, const unsign
 }
 extern "C" int dbx_augment_u8(const unsigned char* in, bf16* out, const float* boxes, const unsigned char* flip, int N,
                               int Hin, int Win, int Cin, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1,
-                              float s2, const int* perm, const int* mixbox, hipStream_t st) {
-  hipLaunchKernelGGL(augment_u8_kernel, row_grid(N * Ho), row_block(Wo), 0, st, in, out, boxes, flip, N, Hin, Win, Cin,
-                     Ho, Wo, m0, m1, m2, s0, s1, s2, perm, mixbox);
+                              float s2, const int* perm, const int* mixbox, hipStream_t st, const int* src_tab,
+                              long long arena16) {
+  if (src_tab)  // the ragged form: `in` is the arena of arena16 16-byte units, Hin / Win unread
+    hipLaunchKernelGGL(augment_u8_kernel<true>, row_grid((long long)N * Ho), row_block(Wo), 0, st, in, out, boxes, flip,
+                       N, Hin, Win, Cin, Ho, Wo, m0, m1, m2, s0, s1, s2, perm, mixbox, src_tab, arena16);
+  else
+    hipLaunchKernelGGL(augment_u8_kernel<false>, row_grid(N * Ho), row_block(Wo), 0, st, in, out, boxes, flip, N, Hin, Win,
+                       Cin, Ho, Wo, m0, m1, m2, s0, s1, s2, perm, mixbox, nullptr, 0ll);
   RET_LAST;
 }
 extern "C" int dbx_augment_mix_u8(const unsigned char* in, bf16* out, const float* boxes, const unsigned char* flip,
                                   int N, int Hin, int Win, int Cin, int Ho, int Wo, float m0, float m1, float m2, float s0,
                                   float s1, float s2, const int* perm, const int* mixbox, const float* blend,
                                   const int* erase, int pixel, unsigned long long seed, const int* rng_offset,
-                                  hipStream_t st) {
+                                  hipStream_t st, const int* src_tab, long long arena16) {
   const AugMix am{blend, erase, rng_offset, seed, pixel};
-  hipLaunchKernelGGL(augment_mix_u8_kernel, row_grid(N * Ho), row_block(Wo), 0, st, in, out, boxes, flip, N, Hin, Win,
-                     Cin, Ho, Wo, m0, m1, m2, s0, s1, s2, perm, mixbox, am);
+  if (src_tab)
+    hipLaunchKernelGGL(augment_mix_u8_kernel<true>, row_grid((long long)N * Ho), row_block(Wo), 0, st, in, out, boxes,
+                       flip, N, Hin, Win, Cin, Ho, Wo, m0, m1, m2, s0, s1, s2, perm, mixbox, am, src_tab, arena16);
+  else
+    hipLaunchKernelGGL(augment_mix_u8_kernel<false>, row_grid(N * Ho), row_block(Wo), 0, st, in, out, boxes, flip, N, Hin,
+                       Win, Cin, Ho, Wo, m0, m1, m2, s0, s1, s2, perm, mixbox, am, nullptr, 0ll);
   RET_LAST;
 }
 extern "C" int dbx_crop_resize_u8(const unsigned char* in, unsigned char* T, int* hist, const float* boxes,
-                                  const unsigned char* flip, int N, int Hin, int Win, int Ho, int Wo, hipStream_t st) {
-  hipLaunchKernelGGL(crop_resize_u8_kernel, row_grid((long long)N * ((Ho + kTaRows - 1) / kTaRows)), row_block(Wo), 0, st,
-                     in, (unsigned*)T, hist, boxes, flip, N, Hin, Win, Ho, Wo);
+                                  const unsigned char* flip, int N, int Hin, int Win, int Ho, int Wo, hipStream_t st,
+                                  const int* src_tab, long long arena16) {
+  const dim3 grid = row_grid((long long)N * ((Ho + kTaRows - 1) / kTaRows));
+  if (src_tab)
+    hipLaunchKernelGGL(crop_resize_u8_kernel<true>, grid, row_block(Wo), 0, st, in, (unsigned*)T, hist, boxes, flip, N,
+                       Hin, Win, Ho, Wo, src_tab, arena16);
+  else
+    hipLaunchKernelGGL(crop_resize_u8_kernel<false>, grid, row_block(Wo), 0, st, in, (unsigned*)T, hist, boxes, flip, N,
+                       Hin, Win, Ho, Wo, nullptr, 0ll);
   RET_LAST;
 }
 extern "C" int dbx_ta_prepare(const int* hist, const int* ops, unsigned char* lut, int* tmean, int N, hipStream_t st) {

@@ -20,6 +20,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <climits>
 #include <cstdint>
 #include <cstring>
 #include <mutex>
@@ -170,6 +171,122 @@ class MDSReader {
     if (!err.empty()) throw std::runtime_error(err);
   }
 
+  // Gather images of their own sizes into one byte arena + table: the layout of data/loader.py pack_layout, which
+  // this mirrors -- sample b has stride_b = ceil16(w_b C) bytes per row and starts at the running sum of h_k stride_k,
+  // table int32 [B][4] = (offset / 16, h, w, stride). `pil` images carry (w, h) each; `ndarray:uint8:<h,w[,c]>` is
+  // uniform. An image above max_h x max_w throws naming the sample, or with `crop` is cut to the limit around its
+  // centre. Row padding bytes are left as they are. Returns the bytes of the arena the batch fills.
+  int64_t gather_ragged(py::array_t<int64_t, py::array::c_style | py::array::forcecast> idx, uintptr_t out_ptr,
+                        int64_t out_bytes, uintptr_t table_ptr, uintptr_t label_ptr, int max_h, int max_w, int C,
+                        bool crop, const std::string& image_col, const std::string& label_col, int nthreads) {
+    const int ic = col(image_col), lc = col(label_col);
+    const std::string& ienc = encs_[ic];
+    const bool pil = ienc == "pil";
+    int64_t nd_h = 0, nd_w = 0, nd_c = 1;
+    if (!pil) {
+      if (ienc.rfind("ndarray:uint8:", 0) != 0)
+        throw std::invalid_argument("native gather needs `pil` or `ndarray:uint8` images, got " + ienc);
+      std::vector<int64_t> dims;
+      size_t pos = std::string("ndarray:uint8:").size();
+      while (pos <= ienc.size()) {
+        const size_t e = std::min(ienc.find(',', pos), ienc.size());
+        dims.push_back(std::stoll(ienc.substr(pos, e - pos)));
+        pos = e + 1;
+      }
+      if (dims.size() < 2 || dims.size() > 3) throw std::invalid_argument("ragged gather needs [H,W] or [H,W,C] arrays");
+      nd_h = dims[0]; nd_w = dims[1]; nd_c = dims.size() == 3 ? dims[2] : 1;
+      if (nd_c != C) throw std::runtime_error("images have " + std::to_string(nd_c) + " channels, loader expects " + std::to_string(C));
+    }
+    if (max_h < 1 || max_w < 1 || C < 1) throw std::invalid_argument("ragged gather: bad limits");
+    const int64_t B = idx.shape(0);
+    const int64_t* ids = idx.data();
+    uint8_t* out = reinterpret_cast<uint8_t*>(out_ptr);
+    int32_t* table = reinterpret_cast<int32_t*>(table_ptr);
+    int64_t* labels = reinterpret_cast<int64_t*>(label_ptr);
+    struct Item { const uint8_t* px; int64_t h, w, ch, cw; };
+    std::vector<Item> items((size_t)B);
+    int64_t used = 0;
+    {
+      py::gil_scoped_release release;
+      // pass 1 (serial: headers only): sizes, the oversize rule, the table
+      for (int64_t b = 0; b < B; ++b) {
+        auto f = field(ids[b], ic);
+        const uint8_t* src = f.first;
+        size_t n = f.second;
+        Item it{};
+        if (pil) {
+          if (n < 12) throw std::runtime_error("corrupt `pil` image " + std::to_string(ids[b]));
+          uint32_t hdr[3];
+          std::memcpy(hdr, src, 12);
+          if (n < 12 + (size_t)hdr[2]) throw std::runtime_error("corrupt `pil` image " + std::to_string(ids[b]));
+          const std::string mode(reinterpret_cast<const char*>(src + 12), hdr[2]);
+          const int mc = mode == "RGB" ? 3 : (mode == "L" ? 1 : -1);
+          if (mc != C)
+            throw std::runtime_error("sample " + std::to_string(ids[b]) + ": mode " + mode + ", loader expects " +
+                                     std::to_string(C) + " channels");
+          it.w = hdr[0]; it.h = hdr[1];
+          src += 12 + hdr[2];
+          n -= 12 + hdr[2];
+        } else {
+          it.h = nd_h; it.w = nd_w;
+        }
+        if (it.h < 1 || it.w < 1 || n != (size_t)it.h * it.w * C) throw std::runtime_error("image payload size mismatch");
+        it.ch = it.h; it.cw = it.w;
+        if (it.h > max_h || it.w > max_w) {
+          if (!crop)
+            throw std::invalid_argument("sample " + std::to_string(ids[b]) + ": " + std::to_string(it.h) + " x " +
+                                     std::to_string(it.w) + " exceeds ragged_max_hw=(" + std::to_string(max_h) + ", " +
+                                     std::to_string(max_w) + ")");
+          it.ch = std::min<int64_t>(it.h, max_h); it.cw = std::min<int64_t>(it.w, max_w);
+        }
+        it.px = src;
+        items[(size_t)b] = it;
+        const int64_t stride = (it.cw * C + 15) / 16 * 16;
+        table[4 * b] = (int32_t)(used / 16); table[4 * b + 1] = (int32_t)it.ch;
+        table[4 * b + 2] = (int32_t)it.cw; table[4 * b + 3] = (int32_t)stride;
+        used += it.ch * stride;
+        if (used > out_bytes || used / 16 > INT32_MAX)
+          throw std::runtime_error("ragged batch of more than " + std::to_string(out_bytes) + " bytes");
+      }
+    }
+    std::string err;
+    std::mutex mu;
+    {
+      py::gil_scoped_release release;
+      auto work = [&](int t, int nt) {
+        for (int64_t b = t; b < B; b += nt) {
+          try {
+            const Item& it = items[(size_t)b];
+            const int64_t y0 = (it.h - it.ch) / 2, x0 = (it.w - it.cw) / 2;
+            uint8_t* dst = out + (size_t)table[4 * b] * 16;
+            const size_t stride = (size_t)table[4 * b + 3], row = (size_t)it.cw * C;
+            for (int64_t y = 0; y < it.ch; ++y)
+              std::memcpy(dst + (size_t)y * stride, it.px + ((size_t)(y0 + y) * it.w + x0) * C, row);
+            if (labels) {
+              auto l = field(ids[b], lc);
+              int64_t v = 0;
+              if (l.second == 8) std::memcpy(&v, l.first, 8);
+              else if (l.second == 4) { int32_t v32; std::memcpy(&v32, l.first, 4); v = v32; }
+              else throw std::runtime_error("unsupported label width");
+              labels[b] = v;
+            }
+          } catch (const std::exception& e) {
+            std::lock_guard<std::mutex> g(mu);
+            if (err.empty()) err = e.what();
+            return;
+          }
+        }
+      };
+      const int nt = std::max(1, std::min<int>(nthreads, (int)B));
+      std::vector<std::thread> th;
+      for (int t = 1; t < nt; ++t) th.emplace_back(work, t, nt);
+      work(0, nt);
+      for (auto& x : th) x.join();
+    }
+    if (!err.empty()) throw std::runtime_error(err);
+    return used;
+  }
+
   py::bytes raw_field(int64_t g, const std::string& column) const {
     auto f = field(g, col(column));
     return py::bytes(reinterpret_cast<const char*>(f.first), f.second);
@@ -192,6 +309,10 @@ void register_runtime(py::module& m) {
       .def("num_samples", &MDSReader::num_samples)
       .def("gather", &MDSReader::gather, py::arg("indices"), py::arg("out_ptr"), py::arg("label_ptr"), py::arg("H"),
            py::arg("W"), py::arg("C"), py::arg("image_col") = "image", py::arg("label_col") = "label",
+           py::arg("nthreads") = 8)
+      .def("gather_ragged", &MDSReader::gather_ragged, py::arg("indices"), py::arg("out_ptr"), py::arg("out_bytes"),
+           py::arg("table_ptr"), py::arg("label_ptr"), py::arg("max_h"), py::arg("max_w"), py::arg("C"),
+           py::arg("crop") = false, py::arg("image_col") = "image", py::arg("label_col") = "label",
            py::arg("nthreads") = 8)
       .def("raw_field", &MDSReader::raw_field);
 }

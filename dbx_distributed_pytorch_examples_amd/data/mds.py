@@ -423,9 +423,27 @@ class StreamingDataset(IterableDataset):
                              [(-1 if z is None else int(z)) for z in self.shards[0].sizes])
 
 
+def resize_shorter_side(img, side: int):
+    """torchvision's ``Resize(side)`` on a PIL image: the shorter side becomes ``side``, the longer one
+    ``int(side * long / short)``; Pillow's antialiased bilinear filter."""
+    w, h = img.size
+    short, long = (w, h) if w <= h else (h, w)
+    if short == side:
+        return img
+    new_long = max(1, int(side * long / short))
+    return img.resize((side, new_long) if w <= h else (new_long, side), Image.BILINEAR)
+
+
 def write_image_dataset_mds(dataset, out: str, image_key: str = "image", label_key: str = "label",
-                            encoding: str = "pil", size_limit: int = 1 << 26, limit: Optional[int] = None) -> int:
-    """Serialise an (image, label) dataset (PIL / uint8 HWC images) to MDS (03a's writer loop)."""
+                            encoding: str = "pil", size_limit: int = 1 << 26, limit: Optional[int] = None,
+                            shorter_side: Optional[int] = None) -> int:
+    """Serialise an (image, label) dataset (PIL / uint8 HWC images) to MDS (03a's writer loop). ``shorter_side``:
+    resize every image with Pillow (antialiased bilinear, the aspect ratio kept) so that its shorter side has this
+    many pixels -- what a ragged loader should read: the GPU crop-resize does not antialias, so write the images
+    near the training size (e.g. 256 for 224 x 224 crops)."""
+    if shorter_side is not None and (isinstance(shorter_side, bool) or not isinstance(shorter_side, int)
+                                     or shorter_side < 1):
+        raise ValueError(f"shorter_side must be an integer >= 1 or None, got {shorter_side!r}")
     n = 0
     with MDSWriter(out, {image_key: encoding, label_key: "int"}, size_limit=size_limit) as w:
         for i in range(len(dataset)):
@@ -434,6 +452,8 @@ def write_image_dataset_mds(dataset, out: str, image_key: str = "image", label_k
             img, y = dataset[i]
             if isinstance(img, np.ndarray):
                 img = Image.fromarray(img if img.ndim == 2 or img.shape[2] != 1 else img[..., 0])
+            if shorter_side is not None:
+                img = resize_shorter_side(img, shorter_side)
             w.write({image_key: img, label_key: int(y)})
             n += 1
     return n

@@ -240,8 +240,11 @@ class AutogradTrainer:
                  mix_switch_prob: float = 0.5, erase_prob: float = 0.0, erase_mode: str = "const",
                  erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3), auto_augment=None, loss: str = "ce",
                  bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False,
-                 drop_path_rate: float = 0.0):
+                 drop_path_rate: float = 0.0, src_ragged=None):
         from ..config import validate_drop_path
+        if src_ragged is not None:  # refused, never ignored
+            raise ValueError(f"src_ragged={src_ragged!r} needs the native training step (NativeTrainer), whose input "
+                             f"kernels crop every image from its own size; the autograd engine takes dense batches")
         if validate_drop_path(drop_path_rate) != 0.0:  # refused, never ignored
             raise ValueError(f"drop_path_rate={drop_path_rate!r} is built into the native training step (NativeTrainer: "
                              f"gates on the blocks' last BatchNorm); the autograd engine runs the module as it is -- "

@@ -158,8 +158,11 @@ class FrozenFeatureTrainer:
                  optim: OptimizerConfig, label_smoothing: float = 0.0, src_hw=None, mean=None, std=None,
                  bucket_cap_mb: float = 64.0, allreduce_dtype=torch.float32, use_graphs: bool = True,
                  auto_augment=None, loss: str = "ce", bce_target_threshold: Optional[float] = None,
-                 bce_sum_classes: bool = False, drop_path_rate: float = 0.0):
+                 bce_sum_classes: bool = False, drop_path_rate: float = 0.0, src_ragged=None):
         from ..config import validate_drop_path
+        if src_ragged is not None:  # refused, never ignored
+            raise ValueError(f"src_ragged={src_ragged!r} needs the native training step (NativeTrainer); the "
+                             f"frozen-backbone trainer takes dense [N, Hs, Ws, C] batches (src_hw)")
         if validate_drop_path(drop_path_rate) != 0.0:  # refused, never ignored
             raise ValueError(f"drop_path_rate={drop_path_rate!r} needs the native training step (NativeTrainer); the "
                              f"frozen-backbone trainer runs its backbone in evaluation mode, which never drops a block")

@@ -303,12 +303,16 @@ def _grad_to_param_layout(prm: torch.Tensor):
 
 def native_module(model: nn.Module, batch: Optional[int] = None, image_hw: Optional[Tuple[int, int]] = (224, 224),
                   device: Optional[torch.device] = None, process_group=None,
-                  drop_path_rate: float = 0.0) -> NativeResNet:
+                  drop_path_rate: float = 0.0, src_ragged=None) -> NativeResNet:
     """Wrap a supported ResNet (torchvision-layout ResNet-18/34/50/..., the CIFAR-stem ResNet-18)
     for a fixed ``batch`` x ``image_hw`` (``batch=None``: for the first training batch's shape);
     see the module docstring. ``drop_path_rate`` other than 0 is refused: the gates are drawn and written per
-    step by NativeTrainer, and an autograd function replayed by a foreign loop has no such step."""
+    step by NativeTrainer, and an autograd function replayed by a foreign loop has no such step. ``src_ragged`` is
+    refused too: the module takes float tensors of one size, not a ragged uint8 source."""
     from ..config import validate_drop_path
+    if src_ragged is not None:  # refused, never ignored
+        raise ValueError(f"src_ragged={src_ragged!r} needs the native training step (NativeTrainer), whose input "
+                         f"kernels crop every image from its own size; native_module takes dense float batches")
     if validate_drop_path(drop_path_rate) != 0.0:  # refused, never ignored
         raise ValueError(f"drop_path_rate={drop_path_rate!r} needs the native training step (NativeTrainer), which "
                          f"draws the per-batch gates each step; native_module has no per-step host stage")

@@ -86,7 +86,8 @@ class NativeTrainer:
                  erase_scale: Tuple[float, float] = (0.02, 1 / 3), erase_ratio: Tuple[float, float] = (0.3, 3.3),
                  auto_augment: Optional[str] = None, ta_num_bins: int = 31, loss: str = "ce",
                  bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False,
-                 ra_num_ops: int = 2, ra_magnitude: int = 9, drop_path_rate: float = 0.0):
+                 ra_num_ops: int = 2, ra_magnitude: int = 9, drop_path_rate: float = 0.0,
+                 src_ragged: Optional[Tuple[int, int]] = None):
         validate_loss(loss, bce_target_threshold, bce_sum_classes)
         self.drop_path_rate = validate_drop_path(drop_path_rate)
         validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, erase_mode, erase_scale,
@@ -122,7 +123,7 @@ class NativeTrainer:
         # parameter copy (the all-gather target the weight preparation reads)
         self.prog = ResNetProgram(model, batch, image_hw, device, src_hw=src_hw, mean=mean, std=std,
                                   param_align=16 * self.world if zero_stage else 16, param16=bool(zero_stage),
-                                  engine=cfg)
+                                  engine=cfg, src_ragged=src_ragged)
         self.prog.build_backward()
         self.opt = optim
         self.smoothing = label_smoothing
@@ -910,18 +911,50 @@ class NativeTrainer:
                     self._post(post)
 
     # ----------------------------------------------------------------------------------
+    def _load_images(self, images_u8: torch.Tensor, src_table, n: int, non_blocking: bool = True) -> None:
+        """``n`` samples into the program's static input buffers, outside any captured graph. Dense: ``images_u8``
+        [n, Hs, Ws, C]. Ragged (``src_ragged``): the packed 1-D bytes of the batch, at most the arena, and its table
+        int32 [n, 4]; rows past ``n`` keep what they held."""
+        p = self.prog
+        if p.src_tab is None:
+            if src_table is not None:
+                raise ValueError("src_table belongs to a ragged trainer (src_ragged=(max_h, max_w)); this one takes "
+                                 "dense [N, Hs, Ws, C] batches")
+            (p.img_u8 if n == p.N else p.img_u8[:n]).copy_(images_u8, non_blocking=non_blocking)
+            return
+        if not isinstance(images_u8, torch.Tensor) or images_u8.dim() != 1 or images_u8.dtype != torch.uint8:
+            raise ValueError(f"a ragged trainer takes the packed 1-D uint8 bytes of the batch and its src_table, got "
+                             f"{getattr(images_u8, 'dtype', type(images_u8))} {tuple(getattr(images_u8, 'shape', ()))}")
+        if src_table is None:
+            raise ValueError("a ragged trainer needs src_table (int32 [n, 4]) with every batch of images")
+        if not isinstance(src_table, torch.Tensor) or src_table.dtype != torch.int32:
+            raise TypeError(f"src_table: expected an int32 tensor [{n}, 4], got "
+                            f"{getattr(src_table, 'dtype', type(src_table))}")
+        if tuple(src_table.shape) != (n, 4):
+            raise ValueError(f"src_table: expected shape ({n}, 4), got {tuple(src_table.shape)}")
+        if images_u8.numel() > p.img_u8.numel():
+            raise ValueError(f"the packed batch has {images_u8.numel()} bytes, the arena of src_ragged="
+                             f"{p.src_ragged} holds {p.img_u8.numel()}")
+        p.img_u8[:images_u8.numel()].copy_(images_u8, non_blocking=non_blocking)
+        p.src_tab[:n].copy_(src_table, non_blocking=non_blocking)
+
     def step(self, images_u8: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None,
-             boxes: Optional[torch.Tensor] = None, flips: Optional[torch.Tensor] = None):
+             boxes: Optional[torch.Tensor] = None, flips: Optional[torch.Tensor] = None,
+             src_table: Optional[torch.Tensor] = None):
         """One training step. ``images_u8`` [N,Hs,Ws,C] uint8, ``labels`` [N] int64, optional
         crop ``boxes`` [N,4] / ``flips`` [N] are copied into the program's static input buffers
-        (pass None to reuse what is already there)."""
+        (pass None to reuse what is already there). A ragged trainer (``src_ragged``) takes the packed 1-D bytes
+        of the batch as ``images_u8`` together with ``src_table`` int32 [N, 4] (data/loader.py ``pack_layout``);
+        ``boxes`` are then in each sample's own coordinates."""
         if self._eval_on:
             # the BN scale / shift buffers the pass prepared once are the training forward's too
             raise RuntimeError("step() inside an evaluation pass: call eval_end() first")
         p = self.prog
         p.training = True
         if images_u8 is not None:
-            p.img_u8.copy_(images_u8, non_blocking=True)
+            self._load_images(images_u8, src_table, p.N)
+        elif src_table is not None:
+            raise ValueError("src_table describes the images it comes with: pass both or neither")
         if labels is not None:
             p.labels.copy_(labels, non_blocking=True)
         if boxes is not None:
@@ -966,7 +999,8 @@ class NativeTrainer:
     # ----------------------------------------------------------------------------------
     @torch.no_grad()
     def evaluate_batch(self, images_u8: torch.Tensor, labels: torch.Tensor,
-                       boxes: Optional[torch.Tensor] = None, use_ema: Optional[bool] = None) -> torch.Tensor:
+                       boxes: Optional[torch.Tensor] = None, use_ema: Optional[bool] = None,
+                       src_table: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Eval-mode forward (running BN stats); returns logits (bf16) and accumulates metrics.
         A short final batch is padded (padding rows get label -> excluded by the caller).
         ``use_ema``: evaluate the averaged weights and running statistics (None: when enabled). Nothing
@@ -978,8 +1012,8 @@ class NativeTrainer:
         p.training = False
         if self.comm_stream is not None:  # the last step's parameter all-gather (ZeRO)
             torch.cuda.current_stream(self.dev).wait_stream(self.comm_stream)
-        n = images_u8.shape[0]
-        p.img_u8[:n].copy_(images_u8)
+        n = int(labels.shape[0]) if p.src_tab is not None else images_u8.shape[0]
+        self._load_images(images_u8, src_table, n, non_blocking=False)
         p.labels[:n].copy_(labels)
         if boxes is not None:
             p.boxes[:n].copy_(boxes)
@@ -1044,18 +1078,19 @@ class NativeTrainer:
         self.eval_graph, self._eval_graph_k = g, self._eval_k
 
     @torch.no_grad()
-    def eval_step(self, images_u8: torch.Tensor, labels: torch.Tensor, boxes: Optional[torch.Tensor] = None) -> None:
+    def eval_step(self, images_u8: torch.Tensor, labels: torch.Tensor, boxes: Optional[torch.Tensor] = None,
+                  src_table: Optional[torch.Tensor] = None) -> None:
         """One batch of ``n <= N`` samples: copied into the static input buffers, rows past ``n`` ignored
-        on the device. Never synchronises. With graphs, a trainer's first two calls run eagerly, the third
+        on the device (a ragged trainer: the packed bytes and ``src_table`` int32 [n, 4], as in :meth:`step`). Never synchronises. With graphs, a trainer's first two calls run eagerly, the third
         captures the eval forward and every later call -- of this pass or any later one, with or without
         the average -- replays that one graph (k is a kernel argument: another top-k captures again)."""
         if not self._eval_on:
             raise RuntimeError("eval_step() without eval_begin()")
         p = self.prog
-        n = int(images_u8.shape[0])
+        n = int(labels.shape[0]) if p.src_tab is not None else int(images_u8.shape[0])
         if not 0 < n <= p.N or labels.shape[0] != n:
             raise ValueError(f"eval_step: {n} images and {labels.shape[0]} labels for a batch of {p.N}")
-        p.img_u8[:n].copy_(images_u8, non_blocking=True)
+        self._load_images(images_u8, src_table, n)
         p.labels[:n].copy_(labels, non_blocking=True)
         if boxes is not None:
             p.boxes[:n].copy_(boxes, non_blocking=True)

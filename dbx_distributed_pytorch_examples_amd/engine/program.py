@@ -159,9 +159,14 @@ class ResNetProgram:
 
     def __init__(self, model: nn.Module, batch: int, image_hw: Tuple[int, int], device: torch.device,
                  src_hw: Optional[Tuple[int, int]] = None, mean=None, std=None, param_align: int = 16,
-                 param16: bool = False, engine: Optional[EngineConfig] = None):
+                 param16: bool = False, engine: Optional[EngineConfig] = None,
+                 src_ragged: Optional[Tuple[int, int]] = None):
         """``image_hw``: network input size; ``src_hw``: size of the uint8 images handed in
         (crop/resize to image_hw happens on the GPU, ``augment_u8``); default = image_hw.
+        ``src_ragged = (max_h, max_w)`` instead of ``src_hw``: the images handed in have sizes of their own, up to
+        this one -- ``img_u8`` is then a flat byte arena and ``src_tab`` the int32 [N, 4] table of the batch in it
+        (data/loader.py ``pack_layout``); both addresses are static, so a captured step follows new bytes and a new
+        table, and ``boxes`` are in each sample's own coordinates.
         ``param_align``: every backward segment's parameter group starts on a multiple of this many
         elements (ZeRO: 16 x world, so a segment splits into equal per-rank parts); ``param16``:
         keep a flat bf16 copy of the parameters (``self.param16``, ZeRO's all-gather target) and
@@ -173,7 +178,12 @@ class ResNetProgram:
         self.model = model
         self.N = batch
         self.H, self.W = image_hw
-        self.src_hw = tuple(src_hw) if src_hw else (self.H, self.W)
+        if src_ragged is not None and src_hw is not None:
+            raise ValueError("src_hw (one size for the batch) and src_ragged (a size per sample) exclude each other")
+        if src_ragged is not None and (len(tuple(src_ragged)) != 2 or min(int(v) for v in src_ragged) < 1):
+            raise ValueError(f"src_ragged is (max_h, max_w), both at least 1, got {src_ragged!r}")
+        self.src_ragged = tuple(int(v) for v in src_ragged) if src_ragged is not None else None
+        self.src_hw = self.src_ragged or (tuple(src_hw) if src_hw else (self.H, self.W))
         self.norm_mean = tuple(mean) if mean else None
         self.norm_std = tuple(std) if std else None
         self.dev = device
@@ -636,8 +646,15 @@ class ResNetProgram:
                                     dtype=torch.float32) if dev.type == "cuda" else None)
         self.labels = torch.zeros(N, device=dev, dtype=torch.int64)
         sh, sw = self.src_hw
-        self.img_u8 = torch.zeros(N, sh, sw, 3 if self.in_ch != 1 else 1, device=dev, dtype=torch.uint8)
-        self.boxes = torch.tensor([[0.0, 0.0, float(sh), float(sw)]] * N, device=dev)  # full-image default
+        self.src_ch = 3 if self.in_ch != 1 else 1
+        self.src_tab = None
+        if self.src_ragged is None:
+            self.img_u8 = torch.zeros(N, sh, sw, self.src_ch, device=dev, dtype=torch.uint8)
+            self.boxes = torch.tensor([[0.0, 0.0, float(sh), float(sw)]] * N, device=dev)  # full-image default
+        else:  # any N images of at most sh x sw; every sample starts as the arena's first pixel
+            self.img_u8 = torch.zeros(N * sh * ((sw * self.src_ch + 15) // 16 * 16), device=dev, dtype=torch.uint8)
+            self.src_tab = torch.tensor([[0, 1, 1, 16]] * N, device=dev, dtype=torch.int32)
+            self.boxes = torch.tensor([[0.0, 0.0, 1.0, 1.0]] * N, device=dev)
         self.flip = torch.zeros(N, device=dev, dtype=torch.uint8)
         self.metrics = torch.zeros(2, device=dev, dtype=torch.float64)  # loss sum, correct (fp64 atomics)
         # BN state arena
@@ -892,8 +909,10 @@ class ResNetProgram:
         mix = self.cutmix and self.training  # (evaluation never augments)
         flip = self.flip if flip is None else flip
         kw = {}
+        if self.src_tab is not None:  # ragged sources: on every path below
+            kw = dict(src=self.src_tab, src_channels=self.src_ch)
         if mix:
-            kw = dict(perm=self.mix_perm, mixbox=self.mix_box)
+            kw.update(perm=self.mix_perm, mixbox=self.mix_box)
             if self.ta_ops is not None or self.mix_blend is not None:  # the mixing arena: blend, erasing
                 kw.update(blend=self.mix_blend, erase=self.erase_box, erase_mode=self.erase_mode,
                           erase_rng=(self.erase_seed, self.erase_off))

@@ -1741,8 +1741,19 @@ def _mix_args(N, perm, mixbox, blend, erase, erase_mode, erase_rng) -> tuple:
     return (_p(perm), _p(mixbox), _p(blend), _p(erase), int(pixel), seed if pixel else 0, _p(offset) if pixel else 0)
 
 
+def _src_args(img, src, N, src_channels, channels, what) -> Tuple[int, int]:
+    """The checked ragged source of an input kernel as its trailing arguments ``(src_tab, arena16)``."""
+    arena16 = _ref.check_ragged_src(img, src, N, src_channels, channels, what)
+    if not img.is_cuda:  # (an arena is addressed in 64 bits: it may exceed the 2^31 elements _chk stops at)
+        raise ValueError("img: must be a GPU tensor")
+    _chk(src, torch.int32, "src", N * 4)
+    return src.data_ptr(), arena16
+
+
 @_dispatch
-def normalize_u8(img, out, mean, std, flip=None):
+def normalize_u8(img, out, mean, std, flip=None, **kw):
+    if kw:  # (src / src_channels: a ragged source is cropped and resized, never normalised in place)
+        return _ref.normalize_u8(img, out, mean, std, flip, **kw)
     N, H, W, Cin = img.shape
     _chk(img, torch.uint8, "img")
     _chk(out, torch.bfloat16, "out", N * H * W * 4)
@@ -1753,7 +1764,7 @@ def normalize_u8(img, out, mean, std, flip=None):
 
 @_dispatch
 def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *, blend=None, erase=None,
-               erase_mode="const", erase_rng=None):
+               erase_mode="const", erase_rng=None, src=None, src_channels=3):
     """uint8 NHWC -> bf16 NHWC4: per-sample crop box [N,4] (y0, x0, h, w; fp32) bilinear-resized to
     out's H x W, optional flip [N] uint8, normalised. CutMix: ``perm`` [N] int32 + ``mixbox`` int32
     [y0, y1, x0, x1] (output coordinates; empty box = no mixing) paste sample perm[n]'s augmented
@@ -1767,10 +1778,21 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *,
     the sample. ``erase_mode`` "const": exactly 0 (normalised space); "pixel": N(0, 1) per pixel and
     channel from Philox counter (s Ho + oy) Wo + ox with ``erase_rng = (seed, offset int32[1] device
     tensor)`` (see :func:`reference.erase_noise`). The pad channel stays 0. Calls without ``blend`` and
-    ``erase`` run the plain kernel."""
-    N, Hin, Win, Cin = img.shape
+    ``erase`` run the plain kernel.
+
+    Ragged source: with ``src`` int32 [N, 4] = (offset / 16, H, W, stride) (data/loader.py ``pack_layout``)
+    ``img`` is the 1-D uint8 arena that holds images of different sizes with ``src_channels`` (1 or 3) channels,
+    N is ``out``'s, and every sample -- a pasted or blended one too -- is cropped from its own image, its box in
+    its own coordinates. A table row that leaves the arena or is malformed reads as (0, 1, 1, 16)
+    (:func:`reference.ragged_rows`). Everything after the crop is the dense call's."""
+    if src is not None:
+        N, Hin, Win, Cin = out.shape[0], 0, 0, src_channels
+        tab = _src_args(img, src, N, src_channels, (1, 3), "augment_u8")
+    else:
+        N, Hin, Win, Cin = img.shape
+        tab = (0, 0)
+        _chk(img, torch.uint8, "img")
     _, Ho, Wo, C4 = out.shape
-    _chk(img, torch.uint8, "img")
     _chk(out, torch.bfloat16, "out", N * Ho * Wo * 4)
     _chk(boxes, torch.float32, "boxes", N * 4)
     if flip is not None:
@@ -1778,9 +1800,9 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *,
     mix = _mix_args(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
     args = (img.data_ptr(), out.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Cin, Ho, Wo, *_norm6(mean, std))
     if blend is None and erase is None:
-        C().augment_u8(*args, *mix[:2], stream_ptr())
+        C().augment_u8(*args, *mix[:2], stream_ptr(), *tab)
     else:
-        C().augment_mix_u8(*args, *mix, stream_ptr())
+        C().augment_mix_u8(*args, *mix, stream_ptr(), *tab)
 
 
 ta_work_words = _ref.ta_work_words  # int32 words of trivial_augment_u8's work buffer for (N, Ho, Wo); with stages=K
@@ -1788,15 +1810,21 @@ ta_work_views = _ref.ta_work_views  # of chain_augment_u8's. Its (T, hist, lut, 
 
 
 @_dispatch
-def crop_resize_u8(img, T, hist, boxes, flip=None):
+def crop_resize_u8(img, T, hist, boxes, flip=None, *, src=None, src_channels=3):
     """uint8 NHWC (3 channels) -> ``T`` uint8 [N, Ho, Wo, 4] = (R, G, B, L): ``augment_u8``'s crop box, bilinear
     resize and flip rounded to uint8 (``(int)(v + 0.5f)``), L Pillow's gray value of the rounded pixel; ADDS the
-    per-sample histograms of the four channels to ``hist`` int32 [N, 4, 256] (the caller zeroes it)."""
-    N, Hin, Win, Cin = img.shape
-    if Cin != 3:
-        raise ValueError(f"crop_resize_u8 takes 3-channel images, got Cin={Cin}")
+    per-sample histograms of the four channels to ``hist`` int32 [N, 4, 256] (the caller zeroes it). ``src``: a
+    ragged source as in :func:`augment_u8` (3 channels only)."""
     _, Ho, Wo, C4 = T.shape
-    _chk(img, torch.uint8, "img")
+    if src is not None:
+        N, Hin, Win = T.shape[0], 0, 0
+        tab = _src_args(img, src, N, src_channels, (3,), "crop_resize_u8")
+    else:
+        N, Hin, Win, Cin = img.shape
+        tab = (0, 0)
+        if Cin != 3:
+            raise ValueError(f"crop_resize_u8 takes 3-channel images, got Cin={Cin}")
+        _chk(img, torch.uint8, "img")
     _chk(T, torch.uint8, "T", N * Ho * Wo * 4)
     _chk(hist, torch.int32, "hist", N * 1024)
     _chk(boxes, torch.float32, "boxes", N * 4)
@@ -1805,7 +1833,7 @@ def crop_resize_u8(img, T, hist, boxes, flip=None):
     if flip is not None:
         _chk(flip, torch.uint8, "flip", N)
     C().crop_resize_u8(img.data_ptr(), T.data_ptr(), hist.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Ho, Wo,
-                       stream_ptr())
+                       stream_ptr(), *tab)
 
 
 @_dispatch
@@ -1844,20 +1872,23 @@ def ta_apply_u8(T, out, ops, lut, tmean, mean, std, *, perm=None, mixbox=None, b
 
 
 def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None, erase=None,
-                       erase_mode="const", erase_rng=None):
+                       erase_mode="const", erase_rng=None, src=None, src_channels=3):
     """``augment_u8`` with TrivialAugmentWide: ``ops`` int32 [N, 8] is one operation per sample (engine/mix.py
     ``sample_trivial_augment``), applied to the uint8 image after crop / resize / flip and before the
     normalisation, erasing and mixing (whose arguments are ``augment_u8``'s). ``work``: an int32 buffer of at
     least ``ta_work_words(N, Ho, Wo)`` words (T, histograms, LUTs, gray means). Three launches and one
     memset: :func:`crop_resize_u8`, :func:`ta_prepare`, :func:`ta_apply_u8`. ValueError: ``Cin != 3``, a
-    table that is not [N, 8], a work buffer that is too small."""
+    table that is not [N, 8], a work buffer that is too small. ``src``: a ragged source as in
+    :func:`augment_u8` (3 channels only); only the crop reads it."""
     N, Ho, Wo, _ = out.shape
-    if img.shape[3] != 3:
+    if src is not None:
+        _ref.check_ragged_src(img, src, N, src_channels, (3,), "trivial_augment_u8")
+    elif img.shape[3] != 3:
         raise ValueError(f"trivial_augment_u8 takes 3-channel images, got Cin={img.shape[3]}")
     _ref.check_ta_ops(ops, N)
     T, hist, lut, tmean = _ref.ta_work_views(work, N, Ho, Wo)
     hist.zero_()
-    crop_resize_u8(img, T, hist, boxes, flip)
+    crop_resize_u8(img, T, hist, boxes, flip, src=src, src_channels=src_channels)
     ta_prepare(hist, ops, lut, tmean)
     ta_apply_u8(T, out, ops, lut, tmean, mean, std, perm=perm, mixbox=mixbox, blend=blend, erase=erase,
                 erase_mode=erase_mode, erase_rng=erase_rng)
@@ -1887,7 +1918,7 @@ def ta_stage_u8(T_in, T_out, hist_out, ops, lut, tmean):
 
 
 def chain_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None, erase=None,
-                     erase_mode="const", erase_rng=None):
+                     erase_mode="const", erase_rng=None, src=None, src_channels=3):
     """:func:`trivial_augment_u8` for a table with a stage axis (RandAugment, AutoAugment): ``ops`` int32
     [K, N, 8], stage-major, 1 <= K <= 4, applies K operations in sequence to each sample, every one on the
     uint8 output of the one before and with that image's own histograms, gray value and gray mean. ``work``: at
@@ -1895,15 +1926,18 @@ def chain_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, 
     :func:`crop_resize_u8`; K - 1 times :func:`ta_prepare` + :func:`ta_stage_u8`; :func:`ta_prepare`;
     :func:`ta_apply_u8` with the last stage's operation and the erasing / mixing arguments. K = 1 issues the
     launches of ``trivial_augment_u8``. ValueError, before any launch: ``Cin != 3``, K outside 1..4, a table
-    that is not [K, N, 8], a work buffer that is too small."""
+    that is not [K, N, 8], a work buffer that is too small. ``src``: a ragged source as in :func:`augment_u8`
+    (3 channels only); only the crop reads it."""
     N, Ho, Wo, _ = out.shape
-    if img.shape[3] != 3:
+    if src is not None:
+        _ref.check_ragged_src(img, src, N, src_channels, (3,), "chain_augment_u8")
+    elif img.shape[3] != 3:
         raise ValueError(f"chain_augment_u8 takes 3-channel images, got Cin={img.shape[3]}")
     Kst = _ref.check_chain_ops(ops, N)
     T, hist, lut, tmean = _ref.ta_work_views(work, N, Ho, Wo, Kst)
     T, hists = T.view(-1, N, Ho, Wo, 4), hist.view(Kst, N, 4, 256)
     hist.zero_()
-    crop_resize_u8(img, T[0], hists[0], boxes, flip)
+    crop_resize_u8(img, T[0], hists[0], boxes, flip, src=src, src_channels=src_channels)
     for i in range(Kst - 1):
         ta_prepare(hists[i], ops[i], lut, tmean)
         ta_stage_u8(T[i & 1], T[(i + 1) & 1], hists[i + 1], ops[i], lut, tmean)

@@ -853,7 +853,11 @@ def clip_factor(work, max_norm):
     return work[2:3]
 
 
-def normalize_u8(img, out, mean, std, flip=None):
+def normalize_u8(img, out, mean, std, flip=None, **kw):
+    if "src" in kw or "src_channels" in kw:
+        raise TypeError("normalize_u8 takes a dense batch: a ragged source is cropped and resized (augment_u8)")
+    if kw:
+        raise TypeError(f"normalize_u8: unexpected keyword {sorted(kw)[0]!r}")
     N, H, W, Cin = img.shape
     f = img.float() / 255.0
     if Cin == 1:
@@ -923,20 +927,82 @@ def erase_noise(seed: int, offset: int, pix) -> torch.Tensor:
     return torch.from_numpy(z.astype(np.float32))
 
 
+# ---------------------------------------------------------------------------------------------
+# Ragged sources: a batch of uint8 images of different sizes is one 1-D byte arena and a table ``src`` int32
+# [N, 4] = (offset / 16, H, W, stride): sample n's row y starts at byte 16 offset + y stride and holds W C pixel
+# bytes (data/loader.py ``pack_layout`` writes stride = ceil16(W C) and offsets that are the running sum of
+# H stride). A row of the table is unusable when its extent leaves the arena (counted in whole 16-byte units,
+# as the kernels get it), H < 1, W < 1, stride < W C or stride % 16 != 0; it then reads as the row
+# (0, 1, 1, 16): the arena's first pixel.
+# ---------------------------------------------------------------------------------------------
+RAGGED_SUBSTITUTE = (0, 1, 1, 16)
+
+
+def check_ragged_src(img, src, N: int, src_channels, channels=(1, 3), what: str = "augment_u8") -> int:
+    """The argument rules of ``src=`` (shared by the kernel wrappers and the CPU path); returns the arena's
+    size in 16-byte units."""
+    if isinstance(src_channels, bool) or not isinstance(src_channels, int) or src_channels not in channels:
+        raise ValueError(f"{what}: src_channels must be one of {tuple(channels)}, got {src_channels!r}")
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.int32:
+        raise TypeError(f"src: expected an int32 tensor [N, 4] (offset / 16, H, W, stride), got "
+                        f"{getattr(src, 'dtype', type(src))}")
+    if tuple(src.shape) != (N, 4) or not src.is_contiguous():
+        raise ValueError(f"src: expected a contiguous table of shape ({N}, 4), got {tuple(src.shape)}")
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8:
+        raise TypeError(f"img: with src it is the uint8 arena, got {getattr(img, 'dtype', type(img))}")
+    if img.dim() != 1 or not img.is_contiguous():
+        raise ValueError(f"img: with src it is the 1-D contiguous arena, got shape {tuple(img.shape)}")
+    if img.numel() < 16:
+        raise ValueError(f"img: an arena holds at least 16 bytes, got {img.numel()}")
+    if img.device != src.device:
+        raise ValueError(f"src is on {src.device}, the arena on {img.device}")
+    return img.numel() // 16
+
+
+def ragged_rows(src, arena16: int, C: int):
+    """The table's rows as the kernels read them: ``[(offset / 16, H, W, stride)]``, an unusable row replaced."""
+    rows = []
+    for off, H, W, rb in src.reshape(-1, 4).tolist():
+        ok = off >= 0 and H >= 1 and W >= 1 and rb % 16 == 0 and rb >= W * C and off + (H * rb) // 16 <= arena16
+        rows.append((off, H, W, rb) if ok else RAGGED_SUBSTITUTE)
+    return rows
+
+
+def ragged_views(img, src, C: int):
+    """Per sample its own uint8 ``[H, W, C]`` view of the arena (row padding left out)."""
+    out = []
+    for off, H, W, rb in ragged_rows(src, img.numel() // 16, C):
+        out.append(img[16 * off:16 * off + H * rb].view(H, rb)[:, :W * C].reshape(H, W, C))
+    return out
+
+
+def _sources(img, src, src_channels, N=None, channels=(1, 3), what="augment_u8"):
+    """The batch as a sequence of per-sample ``[H, W, C]`` images: the dense tensor itself, or the views of a
+    ragged source."""
+    if src is None:
+        return img
+    check_ragged_src(img, src, N, src_channels, channels, what)
+    return ragged_views(img, src, src_channels)
+
+
 def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *, blend=None, erase=None,
-               erase_mode="const", erase_rng=None):
-    seed, offset = check_augment_mix(img.shape[0], perm, mixbox, blend, erase, erase_mode, erase_rng)
+               erase_mode="const", erase_rng=None, src=None, src_channels=3):
+    """The definition of ``kernels.augment_u8``. With ``src`` (int32 [N, 4]) ``img`` is the 1-D arena of a ragged
+    source and every sample is cropped from its own ``[H, W, src_channels]`` view, boxes in its own coordinates."""
+    N = out.shape[0] if src is not None else img.shape[0]
+    img = _sources(img, src, src_channels, N)
+    seed, offset = check_augment_mix(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
     if blend is not None or erase is not None:
         # f_s per source sample (erased where erase[s] says so), then the blend, then the paste
         f = _augment_f32(img, out, boxes, mean, std, flip)
         _mix_tail(f, out, perm, mixbox, blend, erase, erase_mode, seed, offset)
         return
     if perm is not None:  # CutMix: the augmented batch, then the box pasted from sample perm[n]
-        augment_u8(img, out, boxes, mean, std, flip)
+        out.copy_(_augment_f32(img, out, boxes, mean, std, flip).bfloat16())
         y0, y1, x0, x1 = (int(v) for v in mixbox.tolist())
         if y0 < y1 and x0 < x1:
-            src = out.clone()
-            out[:, y0:y1, x0:x1] = src[perm.long()][:, y0:y1, x0:x1]
+            plain = out.clone()
+            out[:, y0:y1, x0:x1] = plain[perm.long()][:, y0:y1, x0:x1]
         return
     out.copy_(_augment_f32(img, out, boxes, mean, std, flip).bfloat16())
 
@@ -973,8 +1039,8 @@ def _mix_tail(f, out, perm, mixbox, blend, erase, erase_mode, seed, offset):
 def _augment_f32(img, out, boxes, mean, std, flip=None):
     """The normalised fp32 batch [N, Ho, Wo, 4] (pad channel 0) of ``augment_u8`` before its rounding."""
     _, Ho, Wo, _ = out.shape
-    dev = img.device
-    res = torch.zeros(img.shape[0], Ho, Wo, 4, device=dev)
+    dev = img[0].device
+    res = torch.zeros(len(img), Ho, Wo, 4, device=dev)
     m = torch.tensor(mean, device=dev)
     s = torch.tensor(std, device=dev)
     for n, v in enumerate(_augment_v255(img, Ho, Wo, boxes, flip)):
@@ -983,12 +1049,13 @@ def _augment_f32(img, out, boxes, mean, std, flip=None):
 
 
 def _augment_v255(img, Ho, Wo, boxes, flip=None):
-    """Per sample, the fp32 bilinear crop-resize [Ho, Wo, 3] in 0..255 (the kernels' expression ``v``)."""
-    N, Hin, Win, Cin = img.shape
-    dev = img.device
+    """Per sample, the fp32 bilinear crop-resize [Ho, Wo, 3] in 0..255 (the kernels' expression ``v``). ``img``:
+    a dense batch, or a sequence of per-sample [H, W, C] images (a ragged source)."""
+    dev = img[0].device
     oy = torch.arange(Ho, device=dev).float()
     ox = torch.arange(Wo, device=dev).float()
-    for n in range(N):
+    for n in range(len(img)):
+        Hin, Win, Cin = img[n].shape
         by, bx, bh, bw = (float(v) for v in boxes[n])
         oxx = (Wo - 1 - ox) if (flip is not None and int(flip[n])) else ox
         sy = (by + (oy + 0.5) * bh / Ho - 0.5).clamp(0, Hin - 1)
@@ -1203,11 +1270,13 @@ def ta_apply_image(a, row, lut=None, mean=None):
     return np.stack([np.asarray(lut)[c][a[..., c]] for c in range(3)], -1).astype(np.uint8)
 
 
-def crop_resize_u8(img, T, hist, boxes, flip=None):
+def crop_resize_u8(img, T, hist, boxes, flip=None, *, src=None, src_channels=3):
     """T uint8 [N, Ho, Wo, 4] = (R, G, B, L) of ``u8 = (int)(v + 0.5f)`` with v the fp32 bilinear expression of
-    ``augment_u8``; adds the per-sample histograms to ``hist`` int32 [N, 4, 256]."""
+    ``augment_u8``; adds the per-sample histograms to ``hist`` int32 [N, 4, 256]. ``src``: as ``augment_u8``."""
     N, Ho, Wo, _ = T.shape
-    if img.shape[3] != 3:
+    if src is not None:
+        img = _sources(img, src, src_channels, N, (3,), "crop_resize_u8")
+    elif img.shape[3] != 3:
         raise ValueError(f"crop_resize_u8 takes 3-channel images, got Cin={img.shape[3]}")
     for n, v in enumerate(_augment_v255(img, Ho, Wo, boxes, flip)):
         u = (v + 0.5).to(torch.int64).clamp(0, 255).to(torch.uint8)
@@ -1246,14 +1315,16 @@ def ta_apply_u8(T, out, ops, lut, tmean, mean, std, *, perm=None, mixbox=None, b
 
 
 def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None,
-                       erase=None, erase_mode="const", erase_rng=None):
+                       erase=None, erase_mode="const", erase_rng=None, src=None, src_channels=3):
     N, Ho, Wo, _ = out.shape
-    if img.shape[3] != 3:
+    if src is not None:
+        check_ragged_src(img, src, N, src_channels, (3,), "trivial_augment_u8")
+    elif img.shape[3] != 3:
         raise ValueError(f"trivial_augment_u8 takes 3-channel images, got Cin={img.shape[3]}")
     check_ta_ops(ops, N)
     T, hist, lut, tmean = ta_work_views(work, N, Ho, Wo)
     hist.zero_()
-    crop_resize_u8(img, T, hist, boxes, flip)
+    crop_resize_u8(img, T, hist, boxes, flip, src=src, src_channels=src_channels)
     ta_prepare(hist, ops, lut, tmean)
     ta_apply_u8(T, out, ops, lut, tmean, mean, std, perm=perm, mixbox=mixbox, blend=blend, erase=erase,
                 erase_mode=erase_mode, erase_rng=erase_rng)
@@ -1305,15 +1376,17 @@ def check_chain_ops(ops, N: int) -> int:
 
 
 def chain_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None,
-                     erase=None, erase_mode="const", erase_rng=None):
+                     erase=None, erase_mode="const", erase_rng=None, src=None, src_channels=3):
     N, Ho, Wo, _ = out.shape
-    if img.shape[3] != 3:
+    if src is not None:
+        check_ragged_src(img, src, N, src_channels, (3,), "chain_augment_u8")
+    elif img.shape[3] != 3:
         raise ValueError(f"chain_augment_u8 takes 3-channel images, got Cin={img.shape[3]}")
     Kst = check_chain_ops(ops, N)
     T, hist, lut, tmean = ta_work_views(work, N, Ho, Wo, Kst)
     T, hist = T.view(-1, N, Ho, Wo, 4), hist.view(Kst, N, 4, 256)
     hist.zero_()
-    crop_resize_u8(img, T[0], hist[0], boxes, flip)
+    crop_resize_u8(img, T[0], hist[0], boxes, flip, src=src, src_channels=src_channels)
     for i in range(Kst - 1):
         ta_prepare(hist[i], ops[i], lut, tmean)
         ta_stage_u8(T[i & 1], T[(i + 1) & 1], hist[i + 1], ops[i], lut, tmean)

@@ -36,7 +36,8 @@ import torch
 from torch.utils.data import DataLoader, Dataset
 
 from ..config import (TrainConfig, auto_augment_options, from_deepspeed, has_param_groups, loss_options, mix_options,
-                      mixes_batches, parse_duration, to_dict, validate_aug_repeats, validate_drop_path, validate_train)
+                      mixes_batches, parse_duration, ragged_options, to_dict, validate_aug_repeats, validate_drop_path,
+                      validate_train)
 from ..models import build_model
 from ..parallel import dist as ddist
 from ..parallel.sampler import RepeatAugSampler, ShardSampler
@@ -64,14 +65,17 @@ def _log(msg: str):
         print(msg, flush=True)
 
 
-def _uint8_source(ds) -> bool:
-    """Can the native loader consume this dataset (fixed-size uint8 HWC + int label, or MDS)?"""
+def _uint8_source(ds, ragged: bool = False) -> bool:
+    """Can the native loader consume this dataset (fixed-size uint8 HWC + int label, or MDS)? ``ragged``: images of
+    any sizes, decoded PIL images (an ``ImageFolder`` without a transform) included."""
     if hasattr(ds, "native_reader") or hasattr(ds, "shards"):
         return True
     try:
         x, _ = ds[0]
     except Exception:
         return False
+    if ragged and not isinstance(x, (np.ndarray, torch.Tensor)) and hasattr(x, "size") and hasattr(x, "mode"):
+        return x.mode in ("RGB", "L")
     return isinstance(x, np.ndarray) and x.dtype == np.uint8 and x.ndim == 3
 
 
@@ -137,6 +141,9 @@ class _Native:
         h, w, c = _sample_hw(ds)
         s = cfg.data.image_size
         o = cfg.optim
+        # ragged batches: every sample keeps its size (h, w above are sample 0's and unread from here on)
+        self.ragged = rg = ragged_options(cfg.data)
+        src = dict(src_ragged=rg["ragged_max_hw"]) if rg else dict(src_hw=(h, w))
         mean = std = None
         if cfg.data.dataset in ("cifar10", "cifar"):
             from ..data.transforms import CIFAR_MEAN, CIFAR_STD
@@ -146,7 +153,7 @@ class _Native:
         if isinstance(model, FrozenBackboneClassifier):
             from ..engine.frozen_trainer import FrozenFeatureTrainer
             self.tr = FrozenFeatureTrainer(model, cfg.batch_size, (s, s), dev, o,
-                                           label_smoothing=cfg.data.label_smoothing, src_hw=(h, w), mean=mean,
+                                           label_smoothing=cfg.data.label_smoothing, **src, mean=mean,
                                            std=std, bucket_cap_mb=cfg.bucket_cap_mb, allreduce_dtype=ar,
                                            **loss_options(cfg.data))
         else:
@@ -160,14 +167,17 @@ class _Native:
                                                       bias_weight_decay=o.bias_weight_decay),
                                     label_smoothing=cfg.data.label_smoothing, use_graphs=cfg.graphs,
                                     bucket_cap_mb=cfg.bucket_cap_mb, allreduce_dtype=ar,
-                                    src_hw=(h, w), mean=mean, std=std, zero_stage=cfg.zero.stage,
+                                    **src, mean=mean, std=std, zero_stage=cfg.zero.stage,
                                     seed=cfg.seed, grad_accum=cfg.grad_accum, ema_decay=cfg.ema_decay,
                                     ema_warmup=cfg.ema_warmup, **mix_options(cfg.data),
                                     **auto_augment_options(cfg.data), **loss_options(cfg.data),
                                     drop_path_rate=cfg.drop_path_rate)
         self.ema_eval = bool(cfg.ema_eval)
         self.eval_topk, self.eval_graph = _eval_topk(cfg), bool(cfg.eval_graph)
-        if not cfg.data.augment:
+        if rg:  # torchvision's RandomResizedCrop + flip on the original image; else Resize(shorter side to s)
+            aug = (AugmentSpec(mode="random_resized_crop", hflip=True) if cfg.data.augment
+                   else AugmentSpec(mode="resize_center_crop", crop_frac=1.0))
+        elif not cfg.data.augment:
             aug = AugmentSpec()
         elif (h, w) == (s, s) and s <= 64:
             aug = AugmentSpec(mode="random_crop", pad=4 if s == 32 else 0, hflip=True)
@@ -180,8 +190,10 @@ class _Native:
         self.loader = NativeImageLoader(ds, cfg.batch_size, (h, w), dev, channels=c, augment=aug, out_hw=(s, s),
                                         indices_fn=(lambda e: (sampler.set_epoch(e), sampler.indices().numpy())[1])
                                         if sampler else None, seed=cfg.seed + ddist.get_rank(),
-                                        nthreads=max(1, cfg.data.num_workers))
+                                        nthreads=max(1, cfg.data.num_workers), **rg)
         self.eval_spec = AugmentSpec(mode="center_crop" if (h, w) != (s, s) else "none")
+        if rg:  # torchvision's Resize(s / 0.875) + CenterCrop(s), on each image's own size
+            self.eval_spec = AugmentSpec(mode="resize_center_crop", crop_frac=0.875)
         self.in_hw = (h, w)
         self.batch = cfg.batch_size
 
@@ -193,8 +205,11 @@ class _Native:
         return len(self.loader)
 
     def step(self, batch):
-        img, lab, boxes, flips = batch
-        self.tr.step(img, lab, boxes, flips)
+        img, lab, boxes, flips = batch[:4]
+        if self.ragged:
+            self.tr.step(img, lab, boxes, flips, src_table=batch[4])
+        else:
+            self.tr.step(img, lab, boxes, flips)
 
     @staticmethod
     def batch_samples(batch) -> int:
@@ -217,26 +232,29 @@ class _Native:
         h, w, c = _sample_hw(ds)
         ld = NativeImageLoader(ds, self.batch, (h, w), tr.dev, channels=c, augment=self.eval_spec,
                                out_hw=(tr.prog.H, tr.prog.W), drop_last=False,
-                               indices_fn=(lambda e: sampler.indices().numpy()) if sampler else None, prefetch=1)
+                               indices_fn=(lambda e: sampler.indices().numpy()) if sampler else None, prefetch=1,
+                               **self.ragged)
+        tab = (lambda b: dict(src_table=b[4])) if self.ragged else (lambda b: {})
         has_ema = getattr(tr, "ema", None) is not None  # cfg.ema_eval: validate the averaged weights
         k = self.eval_topk  # (0: no top-k count; clipped to the class count where it is used)
         if self.eval_graph and hasattr(tr, "eval_begin"):
             # one prepared pass: a graph replay per batch, metrics on the device, one host read
             tr.eval_begin(use_ema=self.ema_eval if has_ema else None, topk=max(k, 1))  # (clips k itself)
             try:
-                for img, lab, boxes, _ in ld:
-                    tr.eval_step(img, lab, boxes)
+                for b in ld:
+                    tr.eval_step(b[0], b[1], b[2], **tab(b))
             finally:
                 r = tr.eval_end()
             return r.loss_sum, r.top1, (r.topk if k else 0.0), r.count
         stats = torch.zeros(4, device=tr.dev, dtype=torch.float64)  # K.ce_eval's sums, read once
         frozen = not hasattr(tr, "eval_begin")  # frozen backbone: every metric from the device buffer
         loss, corr, n = 0.0, 0.0, 0
-        for img, lab, boxes, _ in ld:
+        for b in ld:
+            img, lab, boxes = b[:3]
             if has_ema:
-                logits = tr.evaluate_batch(img, lab, boxes, use_ema=self.ema_eval)
+                logits = tr.evaluate_batch(img, lab, boxes, use_ema=self.ema_eval, **tab(b))
             else:
-                logits = tr.evaluate_batch(img, lab, boxes)
+                logits = tr.evaluate_batch(img, lab, boxes, **tab(b))
             if frozen or k:
                 K.ce_eval(logits.contiguous(), lab, stats, max(1, min(k, logits.shape[1])))
             if not frozen:  # eval_graph off: the host path (torch CE and argmax on the fp32 logits)
@@ -326,7 +344,7 @@ def _pick_engine(cfg: TrainConfig, model, ds, dev) -> str:
         not any(p.requires_grad for p in model.resnet.parameters() if p is not None and
                 not any(p is q for q in model.resnet.fc.parameters()))
     # (gradient accumulation: the native trainer's micro-steps; the frozen-backbone trainer has none)
-    if dev.type == "cuda" and (supports(model) or frozen) and _uint8_source(ds) \
+    if dev.type == "cuda" and (supports(model) or frozen) and _uint8_source(ds, bool(cfg.data.ragged)) \
             and (cfg.grad_accum == 1 or not frozen) \
             and (not mixes_batches(cfg.data) or not frozen):  # CutMix / MixUp / erasing: the native input kernel
         return "native"
@@ -404,6 +422,13 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
             raise ValueError(f"drop_path_rate={cfg.drop_path_rate} needs the native training step (NativeTrainer, "
                              f"which gates the blocks' last BatchNorm); this run would use the "
                              f"{'frozen-backbone' if engine == 'native' else engine} engine, which drops no block")
+    if cfg.data.ragged:  # refused, never ignored
+        from ..models.wrappers import FrozenBackboneClassifier
+        if engine != "native" or isinstance(model, FrozenBackboneClassifier):
+            raise ValueError(f"data.ragged needs the native training step (NativeTrainer, whose input kernels read "
+                             f"every image at its own size); this run would use the "
+                             f"{'frozen-backbone' if engine == 'native' else engine} engine, which takes one dense "
+                             f"batch")
     if cfg.data.auto_augment is not None:  # refused, never ignored
         from ..models.wrappers import FrozenBackboneClassifier
         if engine != "native" or isinstance(model, FrozenBackboneClassifier):
