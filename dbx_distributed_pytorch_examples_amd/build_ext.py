@@ -21,6 +21,9 @@ from concurrent.futures import ThreadPoolExecutor
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
+# per-file compiler flags. input_resample.hip: no packed fp32 instructions (v_pk_add / mul / fma_f32) in its kernel;
+# every other file keeps the code it always had
+FILE_FLAGS = {"input_resample.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _hipcc() -> str:
@@ -64,7 +67,8 @@ def build(verbose: bool = False, jobs: int = 8, variant: str = "", defines=()) -
         objs.append(o)
         if _newer(o, [s] + headers):
             if s.endswith(".hip"):
-                cmd = [_hipcc(), f"--offload-arch={arch}", "-munsafe-fp-atomics", "-Wno-inline-asm", "-c", s, "-o", o] + common
+                cmd = [_hipcc(), f"--offload-arch={arch}", "-munsafe-fp-atomics", "-Wno-inline-asm", "-c", s, "-o", o] + \
+                    common + FILE_FLAGS.get(os.path.basename(s), [])
             else:
                 cmd = [_hipcc(), "-c", s, "-o", o] + common + ["-fvisibility=hidden"]
             cmds.append(cmd)

@@ -151,6 +151,25 @@ class DataConfig:
     ragged: bool = False
     ragged_max_hw: Tuple[int, int] = (512, 512)
     ragged_oversize: str = "error"
+    # the crop-resize filter of the native input kernels: None (two-tap bilinear), "aa_bilinear", "bicubic" or
+    # "aa_bicubic" (Pillow's antialiased filters: what torchvision's Resize / RandomResizedCrop apply to a PIL image;
+    # the A1-A3 recipes train and validate with bicubic). eval_resample: the evaluation pass's, None = resample.
+    resample: Optional[str] = None
+    eval_resample: Optional[str] = None
+
+
+RESAMPLES = ("aa_bilinear", "bicubic", "aa_bicubic")
+
+
+def resample_options(d: DataConfig) -> Dict[str, Any]:
+    """The native trainer's ``resample`` / ``eval_resample`` from ``cfg.data``, validated (ValueError: anything but
+    None and the three filter names); ``{}`` when both are None."""
+    for nm, v in (("resample", d.resample), ("eval_resample", d.eval_resample)):
+        if v is not None and (not isinstance(v, str) or v not in RESAMPLES):
+            raise ValueError(f"data.{nm} must be None or one of {RESAMPLES}, got {v!r}")
+    if d.resample is None and d.eval_resample is None:
+        return {}
+    return dict(resample=d.resample, eval_resample=d.eval_resample)
 
 
 RAGGED_OVERSIZE = ("error", "crop")
@@ -243,6 +262,7 @@ def validate_data(d: DataConfig) -> None:
     loss_options(d)
     validate_aug_repeats(d.aug_repeats)
     ragged_options(d)
+    resample_options(d)
 
 
 def validate_drop_path(rate: Any) -> float:

@@ -104,13 +104,15 @@ int dbx_clip_factor(const double* sumsq, float max_norm, float* out, hipStream_t
 // ---- input pipeline (input_ops.hip) -----------------------------------------------------------------------------
 // augment_u8, augment_mix_u8 and crop_resize_u8 read a dense batch [N][Hin][Win][Cin], or -- with src_tab, an int32
 // [N][4] table (offset / 16, H, W, stride) -- images of different sizes packed in the byte arena `in` of arena16
-// 16-byte units (Hin / Win are then unread)
+// 16-byte units (Hin / Win are then unread). filter (augment_u8, crop_resize_u8): 0 = their bilinear kernels, 1 =
+// antialiased bilinear, 2 = bicubic, 3 = antialiased bicubic -- Pillow's separable filters, run by resample_u8 in its
+// image mode (augment_u8: perm / mixbox must then be null) and its T mode (crop_resize_u8)
 int dbx_normalize_u8(const unsigned char* in, bf16* out, const unsigned char* flip, int N, int H, int W, int Cin,
                      float m0, float m1, float m2, float s0, float s1, float s2, hipStream_t st);
 int dbx_augment_u8(const unsigned char* in, bf16* out, const float* boxes, const unsigned char* flip, int N, int Hin,
                    int Win, int Cin, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1, float s2,
                    const int* perm, const int* mixbox, hipStream_t st, const int* src_tab = nullptr,
-                   long long arena16 = 0);
+                   long long arena16 = 0, int filter = 0);
 // the augment kernel with a MixUp blend and / or random erasing
 int dbx_augment_mix_u8(const unsigned char* in, bf16* out, const float* boxes, const unsigned char* flip, int N,
                        int Hin, int Win, int Cin, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1,
@@ -120,7 +122,7 @@ int dbx_augment_mix_u8(const unsigned char* in, bf16* out, const float* boxes, c
 // TrivialAugmentWide: source uint8 -> T (R, G, B, L) + histograms; LUTs and gray means; the mixing kernel on T
 int dbx_crop_resize_u8(const unsigned char* in, unsigned char* T, int* hist, const float* boxes,
                        const unsigned char* flip, int N, int Hin, int Win, int Ho, int Wo, hipStream_t st,
-                       const int* src_tab = nullptr, long long arena16 = 0);
+                       const int* src_tab = nullptr, long long arena16 = 0, int filter = 0);
 int dbx_ta_prepare(const int* hist, const int* ops, unsigned char* lut, int* tmean, int N, hipStream_t st);
 int dbx_ta_apply_u8(const unsigned char* T, bf16* out, const int* ops, const unsigned char* lut, const int* tmean,
                     int N, int Ho, int Wo, float m0, float m1, float m2, float s0, float s1, float s2, const int* perm,
@@ -155,5 +157,11 @@ int dbx_dar_launch_multi(float* const* bufs, unsigned* const* flags, unsigned* c
                          long long n, int world, int grid, double timeout_s, hipStream_t st);
 }
 
+// input_resample.hip: what a nonzero filter of dbx_augment_u8 (mode 0: bf16 NHWC4 out) and dbx_crop_resize_u8 (mode 1:
+// T out + hist) forwards to (C++ linkage); -80: a filter outside 1..3, or mode 1 without 3 channels and histograms
+int dbx_resample_u8(int mode, const unsigned char* in, void* out, int* hist, const float* boxes,
+                    const unsigned char* flip, int N, int Hin, int Win, int Cin, int Ho, int Wo, float m0, float m1,
+                    float m2, float s0, float s1, float s2, hipStream_t st, const int* src_tab, long long arena16,
+                    int filter);
 // conv_dgrad.hip: the data-gradient instantiations of the implicit-GEMM kernel (C++ linkage)
 int dbx_dispatch_dgrad(int bm, int bn, const dbx::IGemmArgs& a, bool accum, int epi, int dma, hipStream_t st);

@@ -439,8 +439,9 @@ def write_image_dataset_mds(dataset, out: str, image_key: str = "image", label_k
                             shorter_side: Optional[int] = None) -> int:
     """Serialise an (image, label) dataset (PIL / uint8 HWC images) to MDS (03a's writer loop). ``shorter_side``:
     resize every image with Pillow (antialiased bilinear, the aspect ratio kept) so that its shorter side has this
-    many pixels -- what a ragged loader should read: the GPU crop-resize does not antialias, so write the images
-    near the training size (e.g. 256 for 224 x 224 crops)."""
+    many pixels. A ragged loader whose trainer runs the two-tap bilinear crop-resize (``resample=None``, which does
+    not antialias) should read images written near the training size (e.g. 256 for 224 x 224 crops); with
+    ``resample="aa_bilinear"`` / ``"aa_bicubic"`` the GPU filter antialiases and the original sizes can stay."""
     if shorter_side is not None and (isinstance(shorter_side, bool) or not isinstance(shorter_side, int)
                                      or shorter_side < 1):
         raise ValueError(f"shorter_side must be an integer >= 1 or None, got {shorter_side!r}")

@@ -240,8 +240,12 @@ class AutogradTrainer:
                  mix_switch_prob: float = 0.5, erase_prob: float = 0.0, erase_mode: str = "const",
                  erase_scale=(0.02, 1 / 3), erase_ratio=(0.3, 3.3), auto_augment=None, loss: str = "ce",
                  bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False,
-                 drop_path_rate: float = 0.0, src_ragged=None):
+                 drop_path_rate: float = 0.0, src_ragged=None, resample=None, eval_resample=None):
         from ..config import validate_drop_path
+        if resample is not None or eval_resample is not None:  # refused, never ignored
+            raise ValueError(f"resample={resample!r} / eval_resample={eval_resample!r} select the filter of the native "
+                             f"step's input kernels (NativeTrainer); the autograd engine takes float batches that are "
+                             f"already resized -- give the dataset's Resize its interpolation instead")
         if src_ragged is not None:  # refused, never ignored
             raise ValueError(f"src_ragged={src_ragged!r} needs the native training step (NativeTrainer), whose input "
                              f"kernels crop every image from its own size; the autograd engine takes dense batches")

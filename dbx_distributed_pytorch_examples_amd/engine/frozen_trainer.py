@@ -158,8 +158,12 @@ class FrozenFeatureTrainer:
                  optim: OptimizerConfig, label_smoothing: float = 0.0, src_hw=None, mean=None, std=None,
                  bucket_cap_mb: float = 64.0, allreduce_dtype=torch.float32, use_graphs: bool = True,
                  auto_augment=None, loss: str = "ce", bce_target_threshold: Optional[float] = None,
-                 bce_sum_classes: bool = False, drop_path_rate: float = 0.0, src_ragged=None):
+                 bce_sum_classes: bool = False, drop_path_rate: float = 0.0, src_ragged=None, resample=None,
+                 eval_resample=None):
         from ..config import validate_drop_path
+        if resample is not None or eval_resample is not None:  # refused, never ignored
+            raise ValueError(f"resample={resample!r} / eval_resample={eval_resample!r} need the native training step "
+                             f"(NativeTrainer); the frozen-backbone trainer keeps the bilinear input kernel")
         if src_ragged is not None:  # refused, never ignored
             raise ValueError(f"src_ragged={src_ragged!r} needs the native training step (NativeTrainer); the "
                              f"frozen-backbone trainer takes dense [N, Hs, Ws, C] batches (src_hw)")

@@ -87,8 +87,18 @@ class NativeTrainer:
                  auto_augment: Optional[str] = None, ta_num_bins: int = 31, loss: str = "ce",
                  bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False,
                  ra_num_ops: int = 2, ra_magnitude: int = 9, drop_path_rate: float = 0.0,
-                 src_ragged: Optional[Tuple[int, int]] = None):
+                 src_ragged: Optional[Tuple[int, int]] = None, resample: Optional[str] = None,
+                 eval_resample: Optional[str] = None):
         validate_loss(loss, bce_target_threshold, bce_sum_classes)
+        # resample / eval_resample (None = resample): the crop-resize filter of the input kernels in training and
+        # in evaluation -- "aa_bilinear", "bicubic", "aa_bicubic" (K.augment_u8); None: the two-tap bilinear kernels.
+        # With mixing or erasing the filtered uint8 batch goes through K.trivial_augment_u8 (an Identity table when
+        # there is no policy): 3-channel models only then.
+        K.resample_code(resample), K.resample_code(eval_resample)
+        if resample is not None and model.conv1.in_channels != 3 and (
+                cutmix_alpha > 0 or mixup_alpha > 0 or erase_prob > 0):
+            raise ValueError(f"resample={resample!r} with batch mixing or erasing needs 3-channel images, the model "
+                             f"takes {model.conv1.in_channels}")
         self.drop_path_rate = validate_drop_path(drop_path_rate)
         validate_mix(mixup_alpha, cutmix_alpha, mix_prob, mix_switch_prob, erase_prob, erase_mode, erase_scale,
                      erase_ratio)
@@ -123,7 +133,7 @@ class NativeTrainer:
         # parameter copy (the all-gather target the weight preparation reads)
         self.prog = ResNetProgram(model, batch, image_hw, device, src_hw=src_hw, mean=mean, std=std,
                                   param_align=16 * self.world if zero_stage else 16, param16=bool(zero_stage),
-                                  engine=cfg, src_ragged=src_ragged)
+                                  engine=cfg, src_ragged=src_ragged, resample=resample, eval_resample=eval_resample)
         self.prog.build_backward()
         self.opt = optim
         self.smoothing = label_smoothing
@@ -770,7 +780,7 @@ class NativeTrainer:
                 **({"num_ops": self.prog.ta_stages, "magnitude": m.ra_magnitude if self.auto_augment == "ra" else None}
                    if self.auto_augment in ("ra", "aa_imagenet") else {}),
                 "kernel": ("chain_augment_u8" if self.prog.ta_stages > 1 else
-                           "trivial_augment_u8" if self.prog.ta_ops is not None else
+                           "trivial_augment_u8" if self.prog.ta_ops is not None or self.prog.rs_ops is not None else
                            "augment_mix_u8" if self.prog.mix_blend is not None else "augment_u8")}
 
     def _set_hyper(self, boundary: bool = True):

@@ -160,13 +160,17 @@ class ResNetProgram:
     def __init__(self, model: nn.Module, batch: int, image_hw: Tuple[int, int], device: torch.device,
                  src_hw: Optional[Tuple[int, int]] = None, mean=None, std=None, param_align: int = 16,
                  param16: bool = False, engine: Optional[EngineConfig] = None,
-                 src_ragged: Optional[Tuple[int, int]] = None):
+                 src_ragged: Optional[Tuple[int, int]] = None, resample: Optional[str] = None,
+                 eval_resample: Optional[str] = None):
         """``image_hw``: network input size; ``src_hw``: size of the uint8 images handed in
         (crop/resize to image_hw happens on the GPU, ``augment_u8``); default = image_hw.
         ``src_ragged = (max_h, max_w)`` instead of ``src_hw``: the images handed in have sizes of their own, up to
         this one -- ``img_u8`` is then a flat byte arena and ``src_tab`` the int32 [N, 4] table of the batch in it
         (data/loader.py ``pack_layout``); both addresses are static, so a captured step follows new bytes and a new
         table, and ``boxes`` are in each sample's own coordinates.
+        ``resample`` / ``eval_resample`` (None = ``resample``): the crop-resize filter of the training-mode and the
+        evaluation-mode input, ``"aa_bilinear"``, ``"bicubic"`` or ``"aa_bicubic"`` (``K.augment_u8``); None keeps
+        the two-tap bilinear kernels, and with both None the program allocates and launches what it always did.
         ``param_align``: every backward segment's parameter group starts on a multiple of this many
         elements (ZeRO: 16 x world, so a segment splits into equal per-rank parts); ``param16``:
         keep a flat bf16 copy of the parameters (``self.param16``, ZeRO's all-gather target) and
@@ -184,6 +188,9 @@ class ResNetProgram:
             raise ValueError(f"src_ragged is (max_h, max_w), both at least 1, got {src_ragged!r}")
         self.src_ragged = tuple(int(v) for v in src_ragged) if src_ragged is not None else None
         self.src_hw = self.src_ragged or (tuple(src_hw) if src_hw else (self.H, self.W))
+        K.resample_code(resample), K.resample_code(eval_resample)  # (ValueError for an unknown name)
+        self.resample = resample
+        self.eval_resample = eval_resample if eval_resample is not None else resample
         self.norm_mean = tuple(mean) if mean else None
         self.norm_std = tuple(std) if std else None
         self.dev = device
@@ -692,6 +699,8 @@ class ResNetProgram:
         # the stage-major chain table [K, N, 8] and the work buffer of K.chain_augment_u8
         self.ta_ops = self.ta_work = self.ta_T = self.ta_hist = self.ta_lut = self.ta_mean = None
         self.ta_stages = 0
+        # resample + mixing without a policy: the same pipeline with an all-Identity table of the program's own
+        self.rs_ops = self.rs_work = None
 
     def _pack_wdesc(self, descs) -> torch.Tensor:
         return K.pack_wdesc(descs, self.dev)
@@ -780,7 +789,7 @@ class ResNetProgram:
         if ta and self.in_ch != 3:
             raise ValueError(f"TrivialAugmentWide needs a 3-channel program, this one has in_channels={self.in_ch}")
         dev = self.dev
-        self.enable_cutmix()
+        self.enable_cutmix(_policy=bool(ta))
         if not (blend or erase or ta):
             return
         # one int32 arena [perm N | box 4 | lam 1 | blend 1 | erase 4 N | ta 8 K N] that the trainer refreshes with
@@ -805,9 +814,20 @@ class ResNetProgram:
         self.erase_off = self._erase_ctr.view(torch.int32)[0:1]
         self._pack_step_descs()
 
-    def enable_cutmix(self) -> None:
-        """The CutMix state alone (:meth:`enable_mix` without a blend or erasing)."""
+    def enable_cutmix(self, _policy: bool = False) -> None:
+        """The CutMix state alone (:meth:`enable_mix` without a blend or erasing). With ``resample`` the paste, the
+        blend and the erasing work on the filtered uint8 image, so -- unless an augmentation policy brings its own
+        table and work buffer -- the program allocates an all-Identity op table and the work buffer of
+        ``K.trivial_augment_u8``. 3-channel programs only, as that pipeline."""
         dev = self.dev
+        if self.resample is not None:
+            if self.in_ch != 3:
+                raise ValueError(f"resample={self.resample!r} with batch mixing or erasing runs the uint8 pipeline of "
+                                 f"K.trivial_augment_u8, which needs a 3-channel program; this one has "
+                                 f"in_channels={self.in_ch}")
+            if not _policy:
+                self.rs_ops = torch.zeros(self.N, 8, device=dev, dtype=torch.int32)  # kind 0: Identity
+                self.rs_work = torch.zeros(K.ta_work_words(self.N, self.H, self.W), device=dev, dtype=torch.int32)
         self.cutmix = True
         self.mix_perm = torch.arange(self.N, device=dev, dtype=torch.int32)
         self.mix_box = torch.zeros(4, device=dev, dtype=torch.int32)  # y0, y1, x0, x1 (empty: no mixing)
@@ -916,10 +936,15 @@ class ResNetProgram:
             if self.ta_ops is not None or self.mix_blend is not None:  # the mixing arena: blend, erasing
                 kw.update(blend=self.mix_blend, erase=self.erase_box, erase_mode=self.erase_mode,
                           erase_rng=(self.erase_seed, self.erase_off))
+        rs = self.resample if self.training else self.eval_resample
+        if rs is not None:  # (with no filter the calls below are the ones they always were)
+            kw.update(resample=rs)
         if mix and self.ta_stages > 1:
             K.chain_augment_u8(self.img_u8, self.x4, self.boxes, mean, std, flip, self.ta_ops, self.ta_work, **kw)
         elif mix and self.ta_ops is not None:
             K.trivial_augment_u8(self.img_u8, self.x4, self.boxes, mean, std, flip, self.ta_ops, self.ta_work, **kw)
+        elif mix and rs is not None:  # paste, blend and erase on the filtered uint8 image: the Identity table
+            K.trivial_augment_u8(self.img_u8, self.x4, self.boxes, mean, std, flip, self.rs_ops, self.rs_work, **kw)
         else:
             K.augment_u8(self.img_u8, self.x4, self.boxes, mean, std, flip, **kw)
         if mix:  # the pasted samples' labels (device gather, inside the captured step)

@@ -1764,7 +1764,7 @@ def normalize_u8(img, out, mean, std, flip=None, **kw):
 
 @_dispatch
 def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *, blend=None, erase=None,
-               erase_mode="const", erase_rng=None, src=None, src_channels=3):
+               erase_mode="const", erase_rng=None, src=None, src_channels=3, resample=None):
     """uint8 NHWC -> bf16 NHWC4: per-sample crop box [N,4] (y0, x0, h, w; fp32) bilinear-resized to
     out's H x W, optional flip [N] uint8, normalised. CutMix: ``perm`` [N] int32 + ``mixbox`` int32
     [y0, y1, x0, x1] (output coordinates; empty box = no mixing) paste sample perm[n]'s augmented
@@ -1784,7 +1784,14 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *,
     ``img`` is the 1-D uint8 arena that holds images of different sizes with ``src_channels`` (1 or 3) channels,
     N is ``out``'s, and every sample -- a pasted or blended one too -- is cropped from its own image, its box in
     its own coordinates. A table row that leaves the arena or is malformed reads as (0, 1, 1, 16)
-    (:func:`reference.ragged_rows`). Everything after the crop is the dense call's."""
+    (:func:`reference.ragged_rows`). Everything after the crop is the dense call's.
+
+    ``resample``: ``"aa_bilinear"``, ``"bicubic"`` or ``"aa_bicubic"`` -- Pillow's separable filter over the box
+    (:func:`reference.resample_axis`; antialiased: the support grows with the downscaling factor), rounded once
+    to uint8 and then normalised, by ``resample_u8_kernel`` (csrc/input_resample.hip) in its image mode; dense
+    and ragged sources, 1 or 3 channels. It mixes nothing: with ``perm``, ``mixbox``, ``blend`` or ``erase`` a
+    ValueError that names :func:`trivial_augment_u8`, whose pipeline does. An unknown name: ValueError."""
+    filt = _ref.check_resample_plain(resample, perm, mixbox, blend, erase)
     if src is not None:
         N, Hin, Win, Cin = out.shape[0], 0, 0, src_channels
         tab = _src_args(img, src, N, src_channels, (1, 3), "augment_u8")
@@ -1800,22 +1807,26 @@ def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *,
     mix = _mix_args(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
     args = (img.data_ptr(), out.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Cin, Ho, Wo, *_norm6(mean, std))
     if blend is None and erase is None:
-        C().augment_u8(*args, *mix[:2], stream_ptr(), *tab)
+        C().augment_u8(*args, *mix[:2], stream_ptr(), *tab, filt)
     else:
         C().augment_mix_u8(*args, *mix, stream_ptr(), *tab)
 
 
+resample_code = _ref.resample_code  # the filter code of ``resample=`` (ValueError for an unknown name)
 ta_work_words = _ref.ta_work_words  # int32 words of trivial_augment_u8's work buffer for (N, Ho, Wo); with stages=K
 ta_work_views = _ref.ta_work_views  # of chain_augment_u8's. Its (T, hist, lut, mean) views
 
 
 @_dispatch
-def crop_resize_u8(img, T, hist, boxes, flip=None, *, src=None, src_channels=3):
+def crop_resize_u8(img, T, hist, boxes, flip=None, *, src=None, src_channels=3, resample=None):
     """uint8 NHWC (3 channels) -> ``T`` uint8 [N, Ho, Wo, 4] = (R, G, B, L): ``augment_u8``'s crop box, bilinear
     resize and flip rounded to uint8 (``(int)(v + 0.5f)``), L Pillow's gray value of the rounded pixel; ADDS the
     per-sample histograms of the four channels to ``hist`` int32 [N, 4, 256] (the caller zeroes it). ``src``: a
-    ragged source as in :func:`augment_u8` (3 channels only)."""
+    ragged source as in :func:`augment_u8` (3 channels only). ``resample``: the filter of :func:`augment_u8`
+    instead of the bilinear sample (``resample_u8_kernel`` in its T mode); L and the histograms are those of the
+    filtered, once-rounded pixel."""
     _, Ho, Wo, C4 = T.shape
+    filt = _ref.resample_code(resample)
     if src is not None:
         N, Hin, Win = T.shape[0], 0, 0
         tab = _src_args(img, src, N, src_channels, (3,), "crop_resize_u8")
@@ -1833,7 +1844,7 @@ def crop_resize_u8(img, T, hist, boxes, flip=None, *, src=None, src_channels=3):
     if flip is not None:
         _chk(flip, torch.uint8, "flip", N)
     C().crop_resize_u8(img.data_ptr(), T.data_ptr(), hist.data_ptr(), boxes.data_ptr(), _p(flip), N, Hin, Win, Ho, Wo,
-                       stream_ptr(), *tab)
+                       stream_ptr(), *tab, filt)
 
 
 @_dispatch
@@ -1872,15 +1883,17 @@ def ta_apply_u8(T, out, ops, lut, tmean, mean, std, *, perm=None, mixbox=None, b
 
 
 def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None, erase=None,
-                       erase_mode="const", erase_rng=None, src=None, src_channels=3):
+                       erase_mode="const", erase_rng=None, src=None, src_channels=3, resample=None):
     """``augment_u8`` with TrivialAugmentWide: ``ops`` int32 [N, 8] is one operation per sample (engine/mix.py
     ``sample_trivial_augment``), applied to the uint8 image after crop / resize / flip and before the
     normalisation, erasing and mixing (whose arguments are ``augment_u8``'s). ``work``: an int32 buffer of at
     least ``ta_work_words(N, Ho, Wo)`` words (T, histograms, LUTs, gray means). Three launches and one
     memset: :func:`crop_resize_u8`, :func:`ta_prepare`, :func:`ta_apply_u8`. ValueError: ``Cin != 3``, a
     table that is not [N, 8], a work buffer that is too small. ``src``: a ragged source as in
-    :func:`augment_u8` (3 channels only); only the crop reads it."""
+    :func:`augment_u8` (3 channels only); only the crop reads it. ``resample``: the crop's filter
+    (:func:`crop_resize_u8`); an all-Identity table then mixes and erases the filtered batch and nothing else."""
     N, Ho, Wo, _ = out.shape
+    _ref.resample_code(resample)
     if src is not None:
         _ref.check_ragged_src(img, src, N, src_channels, (3,), "trivial_augment_u8")
     elif img.shape[3] != 3:
@@ -1888,7 +1901,7 @@ def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None
     _ref.check_ta_ops(ops, N)
     T, hist, lut, tmean = _ref.ta_work_views(work, N, Ho, Wo)
     hist.zero_()
-    crop_resize_u8(img, T, hist, boxes, flip, src=src, src_channels=src_channels)
+    crop_resize_u8(img, T, hist, boxes, flip, src=src, src_channels=src_channels, resample=resample)
     ta_prepare(hist, ops, lut, tmean)
     ta_apply_u8(T, out, ops, lut, tmean, mean, std, perm=perm, mixbox=mixbox, blend=blend, erase=erase,
                 erase_mode=erase_mode, erase_rng=erase_rng)
@@ -1918,7 +1931,7 @@ def ta_stage_u8(T_in, T_out, hist_out, ops, lut, tmean):
 
 
 def chain_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None, erase=None,
-                     erase_mode="const", erase_rng=None, src=None, src_channels=3):
+                     erase_mode="const", erase_rng=None, src=None, src_channels=3, resample=None):
     """:func:`trivial_augment_u8` for a table with a stage axis (RandAugment, AutoAugment): ``ops`` int32
     [K, N, 8], stage-major, 1 <= K <= 4, applies K operations in sequence to each sample, every one on the
     uint8 output of the one before and with that image's own histograms, gray value and gray mean. ``work``: at
@@ -1927,8 +1940,9 @@ def chain_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, 
     :func:`ta_apply_u8` with the last stage's operation and the erasing / mixing arguments. K = 1 issues the
     launches of ``trivial_augment_u8``. ValueError, before any launch: ``Cin != 3``, K outside 1..4, a table
     that is not [K, N, 8], a work buffer that is too small. ``src``: a ragged source as in :func:`augment_u8`
-    (3 channels only); only the crop reads it."""
+    (3 channels only); only the crop reads it. ``resample``: the crop's filter (:func:`crop_resize_u8`)."""
     N, Ho, Wo, _ = out.shape
+    _ref.resample_code(resample)
     if src is not None:
         _ref.check_ragged_src(img, src, N, src_channels, (3,), "chain_augment_u8")
     elif img.shape[3] != 3:
@@ -1937,7 +1951,7 @@ def chain_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, 
     T, hist, lut, tmean = _ref.ta_work_views(work, N, Ho, Wo, Kst)
     T, hists = T.view(-1, N, Ho, Wo, 4), hist.view(Kst, N, 4, 256)
     hist.zero_()
-    crop_resize_u8(img, T[0], hists[0], boxes, flip, src=src, src_channels=src_channels)
+    crop_resize_u8(img, T[0], hists[0], boxes, flip, src=src, src_channels=src_channels, resample=resample)
     for i in range(Kst - 1):
         ta_prepare(hists[i], ops[i], lut, tmean)
         ta_stage_u8(T[i & 1], T[(i + 1) & 1], hists[i + 1], ops[i], lut, tmean)

@@ -986,12 +986,22 @@ def _sources(img, src, src_channels, N=None, channels=(1, 3), what="augment_u8")
 
 
 def augment_u8(img, out, boxes, mean, std, flip=None, perm=None, mixbox=None, *, blend=None, erase=None,
-               erase_mode="const", erase_rng=None, src=None, src_channels=3):
+               erase_mode="const", erase_rng=None, src=None, src_channels=3, resample=None):
     """The definition of ``kernels.augment_u8``. With ``src`` (int32 [N, 4]) ``img`` is the 1-D arena of a ragged
-    source and every sample is cropped from its own ``[H, W, src_channels]`` view, boxes in its own coordinates."""
+    source and every sample is cropped from its own ``[H, W, src_channels]`` view, boxes in its own coordinates.
+    ``resample``: the uint8 pixel of :func:`resample_v64`, normalised (no mixing argument then)."""
     N = out.shape[0] if src is not None else img.shape[0]
+    code = check_resample_plain(resample, perm, mixbox, blend, erase)
     img = _sources(img, src, src_channels, N)
     seed, offset = check_augment_mix(N, perm, mixbox, blend, erase, erase_mode, erase_rng)
+    if code:
+        _, Ho, Wo, _ = out.shape
+        f = torch.zeros(N, Ho, Wo, 4)
+        m, sd = torch.tensor(mean), torch.tensor(std)
+        for n, u in enumerate(_resample_u8(img, Ho, Wo, boxes, flip, resample)):
+            f[n, ..., :3] = (u.float() / 255.0 - m) / sd
+        out.copy_(f.bfloat16())
+        return
     if blend is not None or erase is not None:
         # f_s per source sample (erased where erase[s] says so), then the blend, then the paste
         f = _augment_f32(img, out, boxes, mean, std, flip)
@@ -1068,6 +1078,101 @@ def _augment_v255(img, Ho, Wo, boxes, flip=None):
             im = im.expand(Hin, Win, 3)
         im = im[..., :3]
         yield ((im[y0][:, x0] * (1 - wx) + im[y0][:, x1] * wx) * (1 - wy) + (im[y1][:, x0] * (1 - wx) + im[y1][:, x1] * wx) * wy)
+
+
+# ---------------------------------------------------------------------------------------------
+# Resampling filters (csrc/input_resample.hip): ``resample=`` of augment_u8 / crop_resize_u8 / trivial_augment_u8 /
+# chain_augment_u8 replaces the two-tap bilinear sample by Pillow's separable filter -- ``"aa_bilinear"``,
+# ``"bicubic"`` (a = -0.5, no antialiasing) or ``"aa_bicubic"`` -- over the crop box, rounded once to uint8; everything
+# downstream works on that uint8 pixel, as torchvision's transforms do after a resize of a PIL image.
+# ---------------------------------------------------------------------------------------------
+RESAMPLE = {None: 0, "aa_bilinear": 1, "bicubic": 2, "aa_bicubic": 3}  # the kernels' filter codes
+
+
+def resample_code(resample) -> int:
+    """The filter code of ``resample=``; ValueError for anything but None and the three names."""
+    if resample is not None and (not isinstance(resample, str) or resample not in RESAMPLE):
+        raise ValueError(f"resample must be None or one of {tuple(k for k in RESAMPLE if k)}, got {resample!r}")
+    return RESAMPLE[resample]
+
+
+def _rs_filter(x, cubic: bool):
+    import numpy as np
+    x = np.abs(x)
+    if not cubic:
+        return np.where(x < 1.0, 1.0 - x, 0.0)
+    return np.where(x < 1.0, (1.5 * x - 2.5) * x * x + 1.0, np.where(x < 2.0, (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5, 0.0))
+
+
+def resample_axis(b: float, l: float, n: int, W: int, resample: str, flip: bool = False):
+    """One axis of the definition (Pillow's ``precompute_coeffs``), float64: box start ``b``, box length ``l``, ``n``
+    outputs, source size ``W``. Returns the weight matrix [n, W] (row o: the normalised taps of output o, already
+    un-flipped) and the tap counts [n]:
+
+        scale = l / n; fs = max(scale, 1) with antialias, else 1; sup = S fs (S = 1 triangle, 2 cubic)
+        c = b + (o + 0.5) scale; lo = max(0, int(c - sup + 0.5)); hi = min(W, int(c + sup + 0.5))
+        k[x] = filter((x - c + 0.5) / fs) for x in [lo, hi), k /= sum(k)
+
+    The window is clipped to the image, not to the box. Guard: ``hi <= lo`` or ``sum(k) <= 0`` (a box outside the
+    image) gives one tap of weight 1 at ``clamp(floor(c), 0, W - 1)``."""
+    import math
+    import numpy as np
+    code = resample_code(resample)
+    if not code:
+        raise ValueError("resample_axis defines the three filters; resample=None is the bilinear kernels' sample")
+    cubic, aa = code >= 2, code != 2
+    scale = l / n
+    fs = max(scale, 1.0) if aa else 1.0
+    sup = (2.0 if cubic else 1.0) * fs
+    M, taps = np.zeros((n, W)), np.ones(n, dtype=np.int64)
+    clampi = lambda v: int(min(max(v, -2.0 ** 30), 2.0 ** 30))  # noqa: E731  (the kernel's cast)
+    for o in range(n):
+        c = b + ((n - 1 - o if flip else o) + 0.5) * scale
+        lo, hi = max(0, clampi(c - sup + 0.5)), min(W, clampi(c + sup + 0.5))
+        k = _rs_filter((np.arange(lo, max(hi, lo)) - c + 0.5) / fs, cubic)
+        if hi <= lo or k.sum() <= 0:
+            M[o, min(max(clampi(math.floor(c)), 0), W - 1)] = 1.0
+        else:
+            M[o, lo:hi], taps[o] = k / k.sum(), hi - lo
+    return M, taps
+
+
+def resample_v64(img, Ho: int, Wo: int, boxes, flip, resample):
+    """Per sample ``(v, eps)``: the float64 value ``v = sum_y ky sum_x kx px`` [Ho, Wo, 3] of the definition (before
+    its one rounding) and the per-pixel bound [Ho, Wo] on the fp32 kernel's distance from it,
+    ``eps = 255 * 2^-21 * (Tx + Ty) * sum|kx| * sum|ky|`` (a few ulp per fp32 weight, plus the accumulation).
+    ``img``: a dense batch or a sequence of per-sample [H, W, C] images."""
+    import numpy as np
+    for n in range(len(img)):
+        a = img[n].cpu().numpy().astype(np.float64)
+        H, W, C = a.shape
+        if C == 1:
+            a = np.repeat(a, 3, axis=2)
+        by, bx, bh, bw = (float(v) for v in boxes[n])
+        My, ty = resample_axis(by, bh, Ho, H, resample)
+        Mx, tx = resample_axis(bx, bw, Wo, W, resample, flip is not None and bool(int(flip[n])))
+        v = np.einsum("oy,yxc,px->opc", My, a[..., :3], Mx)
+        eps = 255.0 * 2.0 ** -21 * (tx[None, :] + ty[:, None]) * np.abs(Mx).sum(1)[None, :] * np.abs(My).sum(1)[:, None]
+        yield v, eps
+
+
+def _resample_u8(img, Ho, Wo, boxes, flip, resample):
+    """Per sample the definition's uint8 pixel [Ho, Wo, 3]: ``floor(clip(v, 0, 255) + 0.5)``."""
+    import numpy as np
+    for v, _ in resample_v64(img, Ho, Wo, boxes, flip, resample):
+        yield torch.from_numpy(np.floor(np.clip(v, 0.0, 255.0) + 0.5).astype(np.uint8))
+
+
+RESAMPLE_NO_MIX = ("augment_u8(resample=...) crops, resizes and normalises only: perm / mixbox / blend / erase work on "
+                   "the uint8 image, so mix through trivial_augment_u8 (an identity op table mixes and erases alone)")
+
+
+def check_resample_plain(resample, perm, mixbox, blend, erase) -> int:
+    """``augment_u8``'s rule: a filter excludes every mixing argument. Returns the filter code."""
+    code = resample_code(resample)
+    if code and any(t is not None for t in (perm, mixbox, blend, erase)):
+        raise ValueError(RESAMPLE_NO_MIX)
+    return code
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1270,17 +1375,23 @@ def ta_apply_image(a, row, lut=None, mean=None):
     return np.stack([np.asarray(lut)[c][a[..., c]] for c in range(3)], -1).astype(np.uint8)
 
 
-def crop_resize_u8(img, T, hist, boxes, flip=None, *, src=None, src_channels=3):
+def crop_resize_u8(img, T, hist, boxes, flip=None, *, src=None, src_channels=3, resample=None):
     """T uint8 [N, Ho, Wo, 4] = (R, G, B, L) of ``u8 = (int)(v + 0.5f)`` with v the fp32 bilinear expression of
-    ``augment_u8``; adds the per-sample histograms to ``hist`` int32 [N, 4, 256]. ``src``: as ``augment_u8``."""
+    ``augment_u8``; adds the per-sample histograms to ``hist`` int32 [N, 4, 256]. ``src``: as ``augment_u8``.
+    ``resample``: v is the filtered value of :func:`resample_v64` instead."""
     N, Ho, Wo, _ = T.shape
+    code = resample_code(resample)
     if src is not None:
         img = _sources(img, src, src_channels, N, (3,), "crop_resize_u8")
     elif img.shape[3] != 3:
         raise ValueError(f"crop_resize_u8 takes 3-channel images, got Cin={img.shape[3]}")
-    for n, v in enumerate(_augment_v255(img, Ho, Wo, boxes, flip)):
-        u = (v + 0.5).to(torch.int64).clamp(0, 255).to(torch.uint8)
-        T[n].copy_(ta_pack(u))
+    if code:
+        for n, u in enumerate(_resample_u8(img, Ho, Wo, boxes, flip, resample)):
+            T[n].copy_(ta_pack(u))
+    else:
+        for n, v in enumerate(_augment_v255(img, Ho, Wo, boxes, flip)):
+            u = (v + 0.5).to(torch.int64).clamp(0, 255).to(torch.uint8)
+            T[n].copy_(ta_pack(u))
     hist.add_(ta_histograms(T).view(hist.shape))
 
 
@@ -1315,8 +1426,9 @@ def ta_apply_u8(T, out, ops, lut, tmean, mean, std, *, perm=None, mixbox=None, b
 
 
 def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None,
-                       erase=None, erase_mode="const", erase_rng=None, src=None, src_channels=3):
+                       erase=None, erase_mode="const", erase_rng=None, src=None, src_channels=3, resample=None):
     N, Ho, Wo, _ = out.shape
+    resample_code(resample)
     if src is not None:
         check_ragged_src(img, src, N, src_channels, (3,), "trivial_augment_u8")
     elif img.shape[3] != 3:
@@ -1324,7 +1436,7 @@ def trivial_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None
     check_ta_ops(ops, N)
     T, hist, lut, tmean = ta_work_views(work, N, Ho, Wo)
     hist.zero_()
-    crop_resize_u8(img, T, hist, boxes, flip, src=src, src_channels=src_channels)
+    crop_resize_u8(img, T, hist, boxes, flip, src=src, src_channels=src_channels, resample=resample)
     ta_prepare(hist, ops, lut, tmean)
     ta_apply_u8(T, out, ops, lut, tmean, mean, std, perm=perm, mixbox=mixbox, blend=blend, erase=erase,
                 erase_mode=erase_mode, erase_rng=erase_rng)
@@ -1376,8 +1488,9 @@ def check_chain_ops(ops, N: int) -> int:
 
 
 def chain_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, mixbox=None, blend=None,
-                     erase=None, erase_mode="const", erase_rng=None, src=None, src_channels=3):
+                     erase=None, erase_mode="const", erase_rng=None, src=None, src_channels=3, resample=None):
     N, Ho, Wo, _ = out.shape
+    resample_code(resample)
     if src is not None:
         check_ragged_src(img, src, N, src_channels, (3,), "chain_augment_u8")
     elif img.shape[3] != 3:
@@ -1386,7 +1499,7 @@ def chain_augment_u8(img, out, boxes, mean, std, flip, ops, work, *, perm=None, 
     T, hist, lut, tmean = ta_work_views(work, N, Ho, Wo, Kst)
     T, hist = T.view(-1, N, Ho, Wo, 4), hist.view(Kst, N, 4, 256)
     hist.zero_()
-    crop_resize_u8(img, T[0], hist[0], boxes, flip, src=src, src_channels=src_channels)
+    crop_resize_u8(img, T[0], hist[0], boxes, flip, src=src, src_channels=src_channels, resample=resample)
     for i in range(Kst - 1):
         ta_prepare(hist[i], ops[i], lut, tmean)
         ta_stage_u8(T[i & 1], T[(i + 1) & 1], hist[i + 1], ops[i], lut, tmean)

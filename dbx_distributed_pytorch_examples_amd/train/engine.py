@@ -36,7 +36,7 @@ import torch
 from torch.utils.data import DataLoader, Dataset
 
 from ..config import (TrainConfig, auto_augment_options, from_deepspeed, has_param_groups, loss_options, mix_options,
-                      mixes_batches, parse_duration, ragged_options, to_dict, validate_aug_repeats, validate_drop_path,
+                      mixes_batches, parse_duration, ragged_options, resample_options, to_dict, validate_aug_repeats, validate_drop_path,
                       validate_train)
 from ..models import build_model
 from ..parallel import dist as ddist
@@ -171,7 +171,7 @@ class _Native:
                                     seed=cfg.seed, grad_accum=cfg.grad_accum, ema_decay=cfg.ema_decay,
                                     ema_warmup=cfg.ema_warmup, **mix_options(cfg.data),
                                     **auto_augment_options(cfg.data), **loss_options(cfg.data),
-                                    drop_path_rate=cfg.drop_path_rate)
+                                    drop_path_rate=cfg.drop_path_rate, **resample_options(cfg.data))
         self.ema_eval = bool(cfg.ema_eval)
         self.eval_topk, self.eval_graph = _eval_topk(cfg), bool(cfg.eval_graph)
         if rg:  # torchvision's RandomResizedCrop + flip on the original image; else Resize(shorter side to s)
@@ -429,6 +429,17 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
                              f"every image at its own size); this run would use the "
                              f"{'frozen-backbone' if engine == 'native' else engine} engine, which takes one dense "
                              f"batch")
+    if resample_options(cfg.data):  # refused, never ignored
+        from ..models.wrappers import FrozenBackboneClassifier
+        if engine != "native" or isinstance(model, FrozenBackboneClassifier):
+            raise ValueError(f"data.resample={cfg.data.resample!r} / data.eval_resample={cfg.data.eval_resample!r} need "
+                             f"the native training step (NativeTrainer, whose input kernels filter the crop); this "
+                             f"run would use the {'frozen-backbone' if engine == 'native' else engine} engine, which "
+                             f"has no such input stage")
+        in_ch = getattr(getattr(model, "conv1", None), "in_channels", 3)
+        if cfg.data.resample is not None and in_ch != 3 and mixes_batches(cfg.data):
+            raise ValueError(f"data.resample={cfg.data.resample!r} with batch mixing or erasing needs 3-channel "
+                             f"images, the model takes {in_ch}")
     if cfg.data.auto_augment is not None:  # refused, never ignored
         from ..models.wrappers import FrozenBackboneClassifier
         if engine != "native" or isinstance(model, FrozenBackboneClassifier):
