@@ -23,7 +23,8 @@ CSRC = os.path.join(HERE, "csrc")
 BUILD = os.path.join(HERE, "build")
 # per-file compiler flags. input_resample.hip: no packed fp32 instructions (v_pk_add / mul / fma_f32) in its kernel;
 # every other file keeps the code it always had
-FILE_FLAGS = {"input_resample.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"input_resample.hip": _NO_PK_F32, "conv_group.hip": _NO_PK_F32}
 
 
 def _hipcc() -> str:

@@ -616,6 +616,10 @@ static int dispatch_fwd(const IGemmArgs& a, bool pro, bool stats, int dma, hipSt
 extern "C" int dbx_conv_igemm(int mode, int bm, int bn, const IGemmArgs* args, int pro, int stats,
                               int accum, int epi, hipStream_t st, int dma) {
   const IGemmArgs& a = *args;
+  if (mode == 5 || mode == 6) {  // grouped 3x3 (conv_group.hip): plain operands, no fused epilogue
+    if (pro || accum || epi || a.ksplit > 1 || a.fin1 || a.fin2 || a.fin_in || a.res || a.addsrc) return -89;
+    return dbx_group_conv(mode - 5, args, stats, st);
+  }
   if (a.ksplit > 1) {  // split-K: the implicit-GEMM kernel only, every slice non-empty, a counter per tile
     if ((dma != 0 && dma != 1) || mode == STEM || mode == FWD_PATCH || mode == DGRAD_PATCH) return -67;
     if (a.kper < 1 || a.skws == nullptr || a.skcnt == nullptr) return -68;

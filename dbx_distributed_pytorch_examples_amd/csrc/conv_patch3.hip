@@ -652,6 +652,7 @@ extern "C" int dbx_stem_patch(const IGemmArgs* args, int stats, hipStream_t st) 
 // max_wg > 0: at most that many persistent workgroups (a side-stream launch leaving CUs free)
 extern "C" int dbx_wgrad_patch3(const WgradArgs* args, long long ws_cap, hipStream_t st, int max_wg) {
   const WgradArgs& a = *args;
+  if (a.IC < a.OC) return dbx_group_conv_wgrad(args, ws_cap, st, max_wg);  // grouped: conv_group.hip
   if (a.R != 3 || a.S != 3 || a.stride != 1 || a.pad != 1 || a.IC != 64 || a.OC != 64) return -40;
   if (a.OW != 56 || a.IW != 56 || a.OH != a.IH || a.OH % 4 != 0) return -41;
   const int ntile = a.N * a.OH / 4;

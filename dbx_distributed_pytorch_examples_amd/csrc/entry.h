@@ -19,6 +19,11 @@ int dbx_conv_patch3(int mode, const dbx::IGemmArgs* args, int pro, int stats, in
 int dbx_stem_patch(const dbx::IGemmArgs* args, int stats, hipStream_t st);
 int dbx_conv_fast(int mode, int bn, const dbx::IGemmArgs* args, int stats, int accum, int epi, hipStream_t st);
 int dbx_conv_sweep(int mode, const dbx::IGemmArgs* args, int pro, int stats, int accum, int epi, hipStream_t st);
+// grouped 3x3 convs (conv_group.hip): args->IC = channels per group, args->OC = C. dbx_conv_igemm forwards its
+// modes 5 (forward) and 6 (data gradient) to dbx_group_conv as modes 0 / 1; dbx_wgrad_patch3 forwards a grouped
+// geometry (IC < OC) to dbx_group_conv_wgrad, which returns its slab count like the three below
+int dbx_group_conv(int mode, const dbx::IGemmArgs* args, int stats, hipStream_t st);
+int dbx_group_conv_wgrad(const dbx::WgradArgs* args, long long ws_cap, hipStream_t st, int max_wg);
 // these three return the number of fp32 weight-gradient slabs they wrote to args->ws (<= 0: failure)
 int dbx_wgrad_patch3(const dbx::WgradArgs* args, long long ws_cap, hipStream_t st, int max_wg);      // conv_patch3.hip
 int dbx_conv_dwfused(const dbx::DwFusedArgs* args, long long ws_cap, hipStream_t st, int max_cus);  // conv_dwfused.hip

@@ -304,7 +304,7 @@ def _grad_to_param_layout(prm: torch.Tensor):
 def native_module(model: nn.Module, batch: Optional[int] = None, image_hw: Optional[Tuple[int, int]] = (224, 224),
                   device: Optional[torch.device] = None, process_group=None,
                   drop_path_rate: float = 0.0, src_ragged=None, resample=None, eval_resample=None) -> NativeResNet:
-    """Wrap a supported ResNet (torchvision-layout ResNet-18/34/50/..., the CIFAR-stem ResNet-18)
+    """Wrap a supported ResNet (torchvision-layout ResNet-18/34/50/..., ResNeXt, Wide ResNet, the CIFAR-stem ResNet-18)
     for a fixed ``batch`` x ``image_hw`` (``batch=None``: for the first training batch's shape);
     see the module docstring. ``drop_path_rate`` other than 0 is refused: the gates are drawn and written per
     step by NativeTrainer, and an autograd function replayed by a foreign loop has no such step. ``src_ragged`` is

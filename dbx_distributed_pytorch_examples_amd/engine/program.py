@@ -19,7 +19,8 @@ Parameters live in ONE flat fp32 master buffer (conv weights in KRSC order); the
 optimizer already holding them, stay valid; conv weights as channels_last views), so
 ``model.state_dict()`` / ``load_state_dict`` / checkpoint files keep torchvision layouts.
 
-Supported module trees: ``models.ResNet`` (BasicBlock / Bottleneck, any in_channels <= 4) and
+Supported module trees: ``models.ResNet`` (BasicBlock / Bottleneck, any in_channels <= 4; Bottleneck also widened
+(Wide ResNet) or with a grouped 3x3 conv2 (ResNeXt: ``K.group_conv_supported``, 4 to 64 channels per group)) and
 ``models.CifarResNet18``; everything else trains through the autograd path (engine.autograd_step).
 """
 from __future__ import annotations
@@ -96,14 +97,20 @@ class ConvL:
     OH: int
     OW: int
     stem: bool = False
+    groups: int = 1       # > 1: ResNeXt's grouped 3x3 (K.group_conv_*); the weights hold IC / groups input channels
     off: int = 0          # master offset (KRSC fp32)
     w16: Optional[torch.Tensor] = None   # [OC, KTOT] bf16 forward weights
-    wt16: Optional[torch.Tensor] = None  # [IC, R*S*OC] bf16 dgrad weights
-    grad: Optional[torch.Tensor] = None  # fp32 [OC, R*S*IC] view into the flat grad buffer
+    wt16: Optional[torch.Tensor] = None  # [IC, R*S*OC] bf16 dgrad weights (none for a grouped conv)
+    grad: Optional[torch.Tensor] = None  # fp32 [OC, R*S*IC/groups] view into the flat grad buffer
+
+    @property
+    def cpg(self) -> int:
+        """Input channels of one filter (IC / groups)."""
+        return self.IC // self.groups
 
     @property
     def numel(self) -> int:
-        return self.OC * self.IC * self.R * self.S
+        return self.OC * self.cpg * self.R * self.S
 
 
 @dataclass
@@ -333,10 +340,14 @@ class ResNetProgram:
     def _conv(self, name, mod: nn.Conv2d, ih, iw, stem=False) -> ConvL:
         R, S = mod.kernel_size
         st, pad = mod.stride[0], mod.padding[0]
-        if mod.bias is not None or mod.groups != 1 or mod.dilation != (1, 1) or mod.stride[0] != mod.stride[1]:
+        if mod.bias is not None or mod.dilation != (1, 1) or mod.stride[0] != mod.stride[1]:
             raise TypeError(f"{name}: unsupported conv configuration")
+        if mod.groups != 1 and (stem or mod.padding[0] != mod.padding[1] or not K.group_conv_supported(
+                mod.in_channels, mod.out_channels, R, S, st, pad, mod.groups)):
+            raise TypeError(f"{name}: unsupported conv configuration (a grouped conv must be 3x3, pad 1, stride 1 or 2, "
+                            f"IC == OC a multiple of 64, with {K.GROUP_CPG} channels per group)")
         oh, ow = K.conv_out_hw(ih, iw, R, S, st, pad)
-        return ConvL(name, mod, mod.in_channels, mod.out_channels, R, S, st, pad, ih, iw, oh, ow, stem)
+        return ConvL(name, mod, mod.in_channels, mod.out_channels, R, S, st, pad, ih, iw, oh, ow, stem, mod.groups)
 
     def _build_layers(self):
         m = self.model
@@ -357,6 +368,8 @@ class ResNetProgram:
                     c1 = self._conv(f"{pre}.conv1", blk.conv1, h, w)
                     c2 = self._conv(f"{pre}.conv2", blk.conv2, c1.OH, c1.OW)
                     c3 = self._conv(f"{pre}.conv3", blk.conv3, c2.OH, c2.OW)
+                    if c1.groups != 1 or c3.groups != 1:
+                        raise TypeError(f"{pre}: only a bottleneck's conv2 may be grouped")
                     convs = [c1, c2, c3]
                     bns = [BNL(f"{pre}.bn1", blk.bn1, blk.bn1.num_features),
                            BNL(f"{pre}.bn2", blk.bn2, blk.bn2.num_features),
@@ -366,6 +379,8 @@ class ResNetProgram:
                 elif isinstance(blk, (BasicBlock, CifarBlock)):
                     c1 = self._conv(f"{pre}.conv1", blk.conv1, h, w)
                     c2 = self._conv(f"{pre}.conv2", blk.conv2, c1.OH, c1.OW)
+                    if c1.groups != 1 or c2.groups != 1:
+                        raise TypeError(f"{pre}: only a bottleneck's conv2 may be grouped")
                     convs = [c1, c2]
                     bns = [BNL(f"{pre}.bn1", blk.bn1, blk.bn1.num_features),
                            BNL(f"{pre}.bn2", blk.bn2, blk.bn2.num_features)]
@@ -379,6 +394,8 @@ class ResNetProgram:
                     # (named as model.named_parameters() names them: optimizer groups match on these)
                     dsn = "skip_connection" if isinstance(blk, CifarBlock) else "downsample"
                     dsc = self._conv(f"{pre}.{dsn}.0", ds[0], h, w)
+                    if dsc.groups != 1:
+                        raise TypeError(f"{dsc.name}: only a bottleneck's conv2 may be grouped")
                     dsb = BNL(f"{pre}.{dsn}.1", ds[1], ds[1].num_features)
                 last = convs[-1]
                 blk_l = BlockL(kind, convs, bns, dsc, dsb, (h, w, c), (last.OH, last.OW, last.OC))
@@ -446,9 +463,9 @@ class ResNetProgram:
                     src = cv.mod.weight.detach().to(dev, torch.float32)  # [K, C, R, S]
                     flat = self.master[off:off + n]
                     flat.copy_(src.permute(0, 2, 3, 1).reshape(-1))
-                    view = flat.view(cv.OC, cv.R, cv.S, cv.IC).permute(0, 3, 1, 2)  # channels_last view
+                    view = flat.view(cv.OC, cv.R, cv.S, cv.cpg).permute(0, 3, 1, 2)  # channels_last view
                     _repoint(cv.mod.weight, view)
-                    cv.grad = self.grad[off:off + n].view(cv.OC, cv.R * cv.S * cv.IC)
+                    cv.grad = self.grad[off:off + n].view(cv.OC, cv.R * cv.S * cv.cpg)
                     self.param_ranges.append((cv.name + ".weight", off, n))
                 elif kind in ("bn_w", "bn_b"):
                     bn: BNL = obj
@@ -494,9 +511,11 @@ class ResNetProgram:
                 continue
             fwd_off = n16
             n16 += cv.numel
-            tr_off = n16
-            n16 += cv.numel
-            descs.append((cv.off, fwd_off, tr_off, cv.OC, cv.R * cv.S, cv.IC))
+            tr_off = -1  # (a grouped conv's data gradient reads the forward copy: a plain cast)
+            if cv.groups == 1:
+                tr_off = n16
+                n16 += cv.numel
+            descs.append((cv.off, fwd_off, tr_off, cv.OC, cv.R * cv.S, cv.cpg))
             cv._w16_off, cv._wt16_off = fwd_off, tr_off
         fc_off = n16
         n16 += self.fc.weight.numel()
@@ -516,7 +535,8 @@ class ResNetProgram:
                 cv.w16 = self.w16buf[stem_off:stem_off + cv.OC * 256].view(cv.OC, 256)
                 continue
             cv.w16 = self.w16buf[cv._w16_off:cv._w16_off + cv.numel].view(cv.OC, -1)
-            cv.wt16 = self.w16buf[cv._wt16_off:cv._wt16_off + cv.numel].view(cv.IC, -1)
+            if cv.groups == 1:
+                cv.wt16 = self.w16buf[cv._wt16_off:cv._wt16_off + cv.numel].view(cv.IC, -1)
         self.fc_w16 = self.w16buf[fc_off:fc_off + self.fc.weight.numel()].view(self.num_classes, -1)
         self.fc_b16 = self.w16buf[fcb_off:fcb_off + self.num_classes]
         self._wdescs = descs  # + the per-step entries (_pack_step_descs, after the activations exist)
@@ -548,8 +568,10 @@ class ResNetProgram:
             # BN outputs inside the block (inputs of convs 1..n-1), written in backward by the MASK_Y
             # dgrad epilogue that computes them for the ReLU mask anyway: the weight gradient then
             # reads them instead of re-applying BN+ReLU to every staged tile
-            b.acts = [E(N, cv.OH, cv.OW, cv.OC) if self.act_writeback else None for cv in b.convs[:-1]]
-            # acts[j] computed in the forward (eight-wave consumer conv j+1): see self.fast_mat
+            # (the input of a grouped conv, or of one wider than the BN prologue holds, is always materialised)
+            b.acts = [E(N, cv.OH, cv.OW, cv.OC) if self.act_writeback or self._plain_only(b.convs[j + 1]) else None
+                      for j, cv in enumerate(b.convs[:-1])]
+            # acts[j] computed in the forward (eight-wave or grouped consumer conv j+1): see self.fast_mat
             b.mat = [self._materialize(b.convs[j + 1]) and b.acts[j] is not None for j in range(len(b.convs) - 1)]
             h, w, c = b.in_shape
             b.dx = E(N, h, w, c)
@@ -566,7 +588,7 @@ class ResNetProgram:
             # 1/16 of the bytes of re-reading the bf16 output)
             b.obits = torch.empty(N * oh * ow * oc // 8, device=dev, dtype=torch.uint8)
         for cv in self.convs:
-            ktot = 256 if cv.stem else cv.R * cv.S * cv.IC
+            ktot = 256 if cv.stem else cv.R * cv.S * cv.cpg
             wsmax = max(wsmax, cv.OC * ktot)
         # split-K wgrad workspace: up to 64 splits of the largest layer, >= 64 MiB
         self.ws = torch.empty(max(64 * wsmax, 16 << 20), device=dev, dtype=torch.float32)
@@ -1007,6 +1029,10 @@ class ResNetProgram:
                                tail_res_shift=rsh, tail_out=pb.out, tail_bits=pb.obits if tr else None,
                                fin=self._ff(b.bns[0]), fin_in=pfin, fin_in_res=prfin)
                     pending = None
+                elif i > 0 and cv.groups > 1:  # materialised BN output -> grouped 3x3 (csrc/conv_group.hip)
+                    K.bn_apply(b.ys[i - 1], prev_bn.scale, prev_bn.shift, b.acts[i - 1], relu=True)
+                    K.group_conv_fwd(b.acts[i - 1], cv.w16, b.ys[i], groups=cv.groups, stride=cv.stride,
+                                     stats=b.bns[i].stats if tr else None)
                 elif i > 0 and b.mat[i - 1]:  # materialised BN output -> plain-operand (eight-wave) conv
                     K.bn_apply(b.ys[i - 1], prev_bn.scale, prev_bn.shift, b.acts[i - 1], relu=True)
                     K.conv_fwd(b.acts[i - 1], cv.w16, b.ys[i], R=cv.R, S=cv.S, stride=cv.stride, pad=cv.pad,
@@ -1162,6 +1188,13 @@ class ResNetProgram:
         # (ws: the workspace override of a gradient moved to the main stream's tail, see _join_side)
         self._side(lambda batch=None, ws=None: K.conv_wgrad(*args[:3], args[3] if ws is None else ws, *args[4:],
                                                           defer=batch, **kw))
+
+    def _gwgrad(self, dy, x, cv: ConvL):
+        """A grouped conv's weight gradient, queued like :meth:`_wgrad` (its reduction is never deferred)."""
+        kw = dict(groups=cv.groups, stride=cv.stride)
+        if self.side_cu_reserve and self.dev.type == "cuda" and self.overlap_wgrad:
+            kw["cu_reserve"] = self.side_cu_reserve
+        self._side(lambda batch=None, ws=None: K.group_conv_wgrad(dy, x, cv.grad, self.ws if ws is None else ws, **kw))
 
     def _flush_side(self, join_evt: Optional[torch.cuda.Event] = None) -> bool:
         """Fork the side stream once from the main stream and launch the queued weight gradients on it
@@ -1425,6 +1458,14 @@ class ResNetProgram:
             act = b.acts[j - 1]
             kw, src = (pend, gin) if pend else ({}, b.dys[j])
             pend = None
+            if cv.groups > 1:
+                # grouped conv2: plain data gradient, then the ReLU mask and BN1's backward as standalone passes
+                # (not fused into the grouped kernel's epilogue); the weight gradient reads the forward's acts
+                assert not kw, "a grouped conv's BN-backward apply is never folded"
+                K.group_conv_dgrad(src, cv.w16, b.das[j - 1], groups=cv.groups, stride=cv.stride)
+                self._gwgrad(b.dys[j], act, cv)
+                self._bn_bwd(pbn, b.das[j - 1], b.ys[j - 1], b.dys[j - 1], N * pc.OH * pc.OW, K.MASK_Y)
+                continue
             if fuse3 and j == nconv - 1:
                 # one pass: dy3 = BN3-bwd apply(g, y3) -> da2 (+ BN2 moments) and dW3 = dy3^T relu(bn2(y2))
                 K.conv_dwfused(src, kw["bwd_y"], kw["bwd_coeff"], cv.wt16, b.ys[j - 1], pbn.scale, pbn.shift,
@@ -1497,16 +1538,24 @@ class ResNetProgram:
 
     def fwd_conv_flops(self) -> float:
         """FLOPs of the forward convolutions of one step (sizes the wgrad side-stream decision)."""
-        return sum(2.0 * self.N * cv.OH * cv.OW * cv.OC * cv.R * cv.S * cv.IC for cv in self.convs)
+        return sum(2.0 * self.N * cv.OH * cv.OW * cv.OC * cv.R * cv.S * cv.cpg for cv in self.convs)
 
     def _materialize(self, cv: ConvL) -> bool:
         """Does conv ``cv`` (a block-internal 3x3) take a
-        materialised BN output on the eight-wave kernel?"""
+        materialised BN output on the eight-wave kernel (or does it take nothing else)?"""
+        if self._plain_only(cv):
+            return True
         if not (self.fast_mat and self.dev.type == "cuda" and cv.stride == 1
                 and cv.R == 3):
             return False
         t = K.pick_tile(self.N * cv.OH * cv.OW, cv.OC, "fwd0", cv.IC, cv.R, cv.stride)
         return len(t) > 2 and t[2] in (4, 5)
+
+    @staticmethod
+    def _plain_only(cv: ConvL) -> bool:
+        """Convs that cannot apply their input's BN + ReLU while staging: the grouped 3x3 (plain-operand kernels) and
+        inputs wider than the forward prologue's coefficient table (the conv3 of a widened layer4 bottleneck)."""
+        return cv.groups > 1 or cv.IC > K.FWD_PRO_MAXC
 
     def _fuse3(self, b: BlockL, last: bool) -> bool:
         """Run block b's conv3 backward through K.conv_dwfused (the 64 -> 256 conv3 of the 56x56

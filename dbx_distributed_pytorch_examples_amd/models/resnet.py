@@ -7,7 +7,8 @@ The reference pulls its ResNets from torchvision (`models.resnet18/50`, e.g.
 CIFAR-stem ResNet-18 in `/root/reference/setup/resnet18.py:3-67`. torchvision is not
 available on this image, so the architectures are written here directly. State-dict
 keys and parameter counts match torchvision exactly (tests/test_models.py pins
-11,181,642 / 23,528,522 / 25,557,032 params), so checkpoints move both ways.
+11,181,642 / 23,528,522 / 25,557,032 params; tests/test_resnext_cpu.py the ResNeXt and Wide ResNet
+variants), so checkpoints move both ways.
 
 Layout: these are ordinary ``nn.Module`` s (NCHW API, any device). On a GPU the
 training engine (``dbx.engine``) re-plans them as NHWC bf16 programs that run the
@@ -25,12 +26,13 @@ import torch.nn.functional as F
 
 __all__ = [
     "BasicBlock", "Bottleneck", "ResNet", "resnet18", "resnet34", "resnet50",
-    "resnet101", "resnet152", "CifarBlock", "CifarResNet18", "build_model",
+    "resnet101", "resnet152", "resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d", "wide_resnet50_2",
+    "wide_resnet101_2", "CifarBlock", "CifarResNet18", "build_model",
 ]
 
 
-def conv3x3(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
-    return nn.Conv2d(cin, cout, kernel_size=3, stride=stride, padding=1, bias=False)
+def conv3x3(cin: int, cout: int, stride: int = 1, groups: int = 1) -> nn.Conv2d:
+    return nn.Conv2d(cin, cout, kernel_size=3, stride=stride, padding=1, groups=groups, bias=False)
 
 
 def conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
@@ -63,17 +65,18 @@ class BasicBlock(nn.Module):
 
 
 class Bottleneck(nn.Module):
-    """torchvision v1.5 Bottleneck: stride lives on the 3x3 conv (SURVEY.md §2.4 note)."""
+    """torchvision v1.5 Bottleneck: stride lives on the 3x3 conv (SURVEY.md §2.4 note). ``groups`` / ``base_width``
+    (ResNeXt, Wide ResNet): the inner width is ``int(planes * base_width / 64) * groups`` and the 3x3 conv is grouped."""
 
     expansion = 4
 
     def __init__(self, inplanes: int, planes: int, stride: int = 1,
-                 downsample: Optional[nn.Module] = None):
+                 downsample: Optional[nn.Module] = None, groups: int = 1, base_width: int = 64):
         super().__init__()
-        width = planes
+        width = int(planes * base_width / 64) * groups
         self.conv1 = conv1x1(inplanes, width)
         self.bn1 = nn.BatchNorm2d(width)
-        self.conv2 = conv3x3(width, width, stride)
+        self.conv2 = conv3x3(width, width, stride, groups)
         self.bn2 = nn.BatchNorm2d(width)
         self.conv3 = conv1x1(width, planes * self.expansion)
         self.bn3 = nn.BatchNorm2d(planes * self.expansion)
@@ -96,12 +99,16 @@ class ResNet(nn.Module):
 
     ``in_channels`` != 3 reproduces the Ray FashionMNIST variant that swaps conv1 for
     ``Conv2d(1, 64, 7, 2, 3)`` (`/root/reference/05_ray/01_fashion_mnist_pytorch_ray.ipynb:169-174`).
+    ``groups`` / ``width_per_group`` (Bottleneck only): ResNeXt (32 x 4d, 32 x 8d, 64 x 4d) and Wide ResNet (1 x 128).
     """
 
     def __init__(self, block: Type[Union[BasicBlock, Bottleneck]], layers: Sequence[int],
                  num_classes: int = 1000, in_channels: int = 3,
-                 zero_init_residual: bool = False):
+                 zero_init_residual: bool = False, groups: int = 1, width_per_group: int = 64):
         super().__init__()
+        if (groups != 1 or width_per_group != 64) and block is not Bottleneck:
+            raise ValueError("groups / width_per_group need the Bottleneck block")
+        self.groups, self.base_width = groups, width_per_group
         self.block_type = block
         self.layers_cfg = list(layers)
         self.num_classes = num_classes
@@ -125,10 +132,11 @@ class ResNet(nn.Module):
                 conv1x1(self.inplanes, planes * block.expansion, stride),
                 nn.BatchNorm2d(planes * block.expansion),
             )
-        layers: List[nn.Module] = [block(self.inplanes, planes, stride, downsample)]
+        kw = dict(groups=self.groups, base_width=self.base_width) if block is Bottleneck else {}
+        layers: List[nn.Module] = [block(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
-            layers.append(block(self.inplanes, planes))
+            layers.append(block(self.inplanes, planes, **kw))
         return nn.Sequential(*layers)
 
     def forward_features(self, x: torch.Tensor) -> torch.Tensor:
@@ -174,6 +182,26 @@ def resnet101(num_classes: int = 1000, **kw) -> ResNet:
 
 def resnet152(num_classes: int = 1000, **kw) -> ResNet:
     return ResNet(Bottleneck, [3, 8, 36, 3], num_classes=num_classes, **kw)
+
+
+def resnext50_32x4d(num_classes: int = 1000, **kw) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes=num_classes, groups=32, width_per_group=4, **kw)
+
+
+def resnext101_32x8d(num_classes: int = 1000, **kw) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 23, 3], num_classes=num_classes, groups=32, width_per_group=8, **kw)
+
+
+def resnext101_64x4d(num_classes: int = 1000, **kw) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 23, 3], num_classes=num_classes, groups=64, width_per_group=4, **kw)
+
+
+def wide_resnet50_2(num_classes: int = 1000, **kw) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 6, 3], num_classes=num_classes, width_per_group=128, **kw)
+
+
+def wide_resnet101_2(num_classes: int = 1000, **kw) -> ResNet:
+    return ResNet(Bottleneck, [3, 4, 23, 3], num_classes=num_classes, width_per_group=128, **kw)
 
 
 # --------------------------------------------------------------------------------------
@@ -230,6 +258,8 @@ class CifarResNet18(nn.Module):
 _FACTORIES: dict = {
     "resnet18": resnet18, "resnet34": resnet34, "resnet50": resnet50,
     "resnet101": resnet101, "resnet152": resnet152,
+    "resnext50_32x4d": resnext50_32x4d, "resnext101_32x8d": resnext101_32x8d, "resnext101_64x4d": resnext101_64x4d,
+    "wide_resnet50_2": wide_resnet50_2, "wide_resnet101_2": wide_resnet101_2,
     "cifar_resnet18": lambda num_classes=10, **kw: CifarResNet18(num_classes, **kw),
 }
 

@@ -31,6 +31,7 @@ _E = EngineConfig.current  # kernel-selection switches (engine_config.py; DBX_EN
 FWD, DGRAD, STEM, FWD_PATCH, DGRAD_PATCH = 0, 1, 2, 3, 4
 _SPLITK = ("ksplit", "kper", "skws", "skcnt")  # conv_igemm's names for what conv_splitk returns
 MASK_NONE, MASK_OUT, MASK_Y = 0, 1, 2
+FWD_PRO_MAXC = 512  # input channels a forward BN prologue holds (csrc/conv_igemm_kernel.h PRO_MAXC; the tail's: 1024)
 
 
 _POST_LAUNCH = None
@@ -972,6 +973,78 @@ def conv_dwfused(g, y3, coeff, wt16, y2, scale2, shift2, mean2, invstd2, bstats2
                          ws_cap=ws.numel(), M=M, K=Kc, C=Cc, nshard=nsh2, st=stream_ptr(), max_cus=int(cus))
     C().wgrad_reduce(ws.data_ptr(), dw.data_ptr(), Kc * Cc, n, 1.0, 0, stream_ptr())
     return da
+
+
+# --------------------------------------------------------------------------------------
+# grouped 3x3 convs (csrc/conv_group.hip): ResNeXt's conv2
+# --------------------------------------------------------------------------------------
+GROUP_FWD, GROUP_DGRAD = 5, 6  # conv_igemm modes forwarded to dbx_group_conv
+GROUP_CPG = (4, 8, 16, 32, 64)
+
+
+def group_conv_supported(IC: int, OC: int, R: int, S: int, stride: int, pad: int, groups: int) -> bool:
+    """The grouped convs the kernels cover: 3x3, pad 1, stride 1 or 2, IC == OC a multiple of 64, and 4, 8, 16, 32
+    or 64 channels per group."""
+    return (groups > 1 and IC == OC and OC % 64 == 0 and OC % groups == 0 and OC // groups in GROUP_CPG
+            and (R, S, pad) == (3, 3, 1) and stride in (1, 2))
+
+
+def _chk_group(x, y, w16, groups: int, stride: int, what: str) -> Tuple[int, ...]:
+    """``x`` [N, IH, IW, C] the conv's input side, ``y`` [N, OH, OW, C] its output side, ``w16`` [C, 9 * cpg] or None."""
+    N, IH, IW, Cc = x.shape
+    if not group_conv_supported(Cc, Cc, 3, 3, stride, 1, groups):
+        raise ValueError(f"{what}: needs a 3x3 pad-1 stride-1/2 conv with IC == OC % 64 == 0 and {GROUP_CPG} channels "
+                         f"per group; got C={Cc}, groups={groups}, stride={stride}")
+    OH, OW = conv_out_hw(IH, IW, 3, 3, stride, 1)
+    cpg = Cc // groups
+    _chk(x, torch.bfloat16, "x / dx")
+    _chk(y, torch.bfloat16, "out / dy", N * OH * OW * Cc)
+    if w16 is not None:
+        _chk(w16, torch.bfloat16, "w16", Cc * 9 * cpg)
+        if w16.data_ptr() % 16:
+            raise ValueError(f"{what}: the weights must be 16-byte aligned")
+    if max(IH * IW, OH * OW) * Cc * 2 >= 2 ** 31:
+        raise ValueError(f"{what}: one image exceeds the kernels' 32-bit offset range")
+    return N, IH, IW, Cc, OH, OW, cpg
+
+
+@_dispatch
+def group_conv_fwd(x, w16, out, *, groups, stride, stats=None):
+    """out [N, OH, OW, C] = grouped 3x3 pad-1 conv of x [N, IH, IW, C] with ``w16`` [C, 9 * C / groups] (KRSC within
+    the group); ``stats``: the per-channel sum / sum of squares of the rounded outputs added to its shards."""
+    N, IH, IW, Cc, OH, OW, cpg = _chk_group(x, out, w16, groups, stride, "group_conv_fwd")
+    nsh = _chk_stats(stats, "stats", Cc) if stats is not None else 1
+    C().conv_igemm(mode=GROUP_FWD, bm=0, bn=0, x=x.data_ptr(), w=w16.data_ptr(), y=out.data_ptr(), stats=_p(stats),
+                   nshard=nsh, N=N, IH=IH, IW=IW, IC=cpg, OH=OH, OW=OW, OC=Cc, R=3, S=3, stride=stride, pad=1, nr=3,
+                   ns=3, r0=0, s0=0, FH=OH, FW=OW, st=stream_ptr(), dma=0)
+    return out
+
+
+@_dispatch
+def group_conv_dgrad(dy, w16, dx, *, groups, stride):
+    """dx [N, IH, IW, C] = data gradient of :func:`group_conv_fwd` from dy [N, OH, OW, C], one launch at either
+    stride; reads the forward weights (the in-group transpose happens while they are expanded)."""
+    N, IH, IW, Cc, OH, OW, cpg = _chk_group(dx, dy, w16, groups, stride, "group_conv_dgrad")
+    C().conv_igemm(mode=GROUP_DGRAD, bm=0, bn=0, x=dy.data_ptr(), w=w16.data_ptr(), y=dx.data_ptr(), nshard=1, N=N,
+                   IH=IH, IW=IW, IC=cpg, OH=OH, OW=OW, OC=Cc, R=3, S=3, stride=stride, pad=1, nr=3, ns=3, r0=0, s0=0,
+                   FH=IH, FW=IW, st=stream_ptr(), dma=0)
+    return dx
+
+
+@_dispatch
+def group_conv_wgrad(dy, x, dw, ws, *, groups, stride, scale=1.0, accumulate=False, cu_reserve=0):
+    """dw [C, 9 * C / groups] (fp32) = scale * weight gradient of :func:`group_conv_fwd` (+ dw): one fp32 slab per
+    workgroup range in ``ws``, summed in fixed order by ``wgrad_reduce``. ``cu_reserve``: as ``conv_wgrad``."""
+    N, IH, IW, Cc, OH, OW, cpg = _chk_group(x, dy, None, groups, stride, "group_conv_wgrad")
+    _chk(dw, torch.float32, "dw", Cc * 9 * cpg)
+    _chk(ws, torch.float32, "ws")
+    if 2 * Cc * 9 * cpg > ws.numel():
+        raise ValueError("group_conv_wgrad: workspace too small")
+    nsl = C().wgrad_patch3(dy=dy.data_ptr(), x=x.data_ptr(), ws=ws.data_ptr(), ws_cap=ws.numel(), N=N, IH=IH, IW=IW,
+                           IC=cpg, OH=OH, OW=OW, OC=Cc, R=3, S=3, stride=stride, pad=1, st=stream_ptr(),
+                           max_wg=max(Cc // 64, num_cus() - cu_reserve) if cu_reserve > 0 else 0)
+    C().wgrad_reduce(ws.data_ptr(), dw.data_ptr(), Cc * 9 * cpg, nsl, float(scale), int(accumulate), stream_ptr())
+    return dw
 
 
 # --------------------------------------------------------------------------------------

@@ -159,6 +159,37 @@ def conv_wgrad(dy, x, dw, ws, *, R, S, stride, pad, in_scale=None, in_shift=None
     return dw
 
 
+def _group_w(w16, groups):
+    """[C, 9 * cpg] (KRSC within the group) -> conv2d's [C, cpg, 3, 3] fp32."""
+    Cc = w16.shape[0]
+    return w16.float().view(Cc, 3, 3, Cc // groups).permute(0, 3, 1, 2)
+
+
+def group_conv_fwd(x, w16, out, *, groups, stride, stats=None):
+    y = _nhwc(F.conv2d(_nchw(x.float()), _group_w(w16, groups), stride=stride, padding=1, groups=groups)).bfloat16()
+    out.copy_(y.reshape(out.shape))
+    if stats is not None:
+        _add_stats(stats, out)
+    return out
+
+
+def group_conv_dgrad(dy, w16, dx, *, groups, stride):
+    N, H, W, Cc = dx.shape
+    g = torch.nn.grad.conv2d_input((N, Cc, H, W), _group_w(w16, groups), _nchw(dy.float()), stride=stride, padding=1,
+                                   groups=groups)
+    dx.copy_(_nhwc(g).bfloat16())
+    return dx
+
+
+def group_conv_wgrad(dy, x, dw, ws, *, groups, stride, scale=1.0, accumulate=False, cu_reserve=0):
+    Cc = x.shape[-1]
+    g = torch.nn.grad.conv2d_weight(_nchw(x.float()), (Cc, Cc // groups, 3, 3), _nchw(dy.float()), stride=stride,
+                                    padding=1, groups=groups)
+    g = (g.permute(0, 2, 3, 1) * scale).reshape(dw.shape)  # KRSC within the group
+    dw.copy_(g + dw if accumulate else g)
+    return dw
+
+
 def conv_dwfused(g, y3, coeff, wt16, y2, scale2, shift2, mean2, invstd2, bstats2, da, dw, ws, cus=0):
     """Fused bottleneck-conv3 backward = BN3-backward apply -> MASK_Y dgrad + weight gradient."""
     from types import SimpleNamespace
