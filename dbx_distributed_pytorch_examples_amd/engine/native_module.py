@@ -46,6 +46,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from .program import ResNetProgram, supports, release_dead_graphs
+from .schedule import ScheduleContext
 
 
 class _NativeFn(torch.autograd.Function):
@@ -99,7 +100,10 @@ class NativeResNet(nn.Module):
 
     def _build(self, batch: int, image_hw: Tuple[int, int]) -> None:
         """Compile the program (parameters / BN buffers move into its flat buffers, same objects)."""
-        self.prog = p = ResNetProgram(self.model, batch, image_hw, self.dev)
+        # (world > 1: weight gradients in order on the main stream, beside the module's own comm stream)
+        cuda = self.dev.type == "cuda"
+        self.prog = p = ResNetProgram(self.model, batch, image_hw, self.dev,
+                                      context=ScheduleContext(cuda=cuda, in_order_wgrads=self.world > 1))
         p.build_backward()
         self._grad_views = []
         for prm in self.model.parameters():
@@ -114,12 +118,8 @@ class NativeResNet(nn.Module):
             for rs in p.segment_param_ranges():
                 self._seg_ranges.append((min(r[1] for r in rs), max(r[1] + (r[2] + 15) // 16 * 16 for r in rs))
                                         if rs else None)
-            if p.dev.type == "cuda":
+            if cuda:
                 self._comm = torch.cuda.Stream(device=p.dev, priority=-1)
-                # next to the comm stream the wgrad side stream costs more than it overlaps
-                # (NativeTrainer, profiles/r2s2_multirank/): weight gradients run on the main stream
-                p.overlap_wgrad = False
-                p.side_batch = p.side_block = False
 
     # ------------------------------------------------------------------------------
     def _init_distributed(self):

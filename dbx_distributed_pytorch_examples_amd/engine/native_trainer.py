@@ -41,6 +41,7 @@ from ..utils.profiling import PhaseTimer
 from .hyper import DeviceHyper
 from .mix import MixDraw, MixSampler, auto_augment_stages, validate_auto_augment, validate_mix
 from .program import ResNetProgram, release_dead_graphs
+from .schedule import ScheduleContext
 
 
 @dataclass
@@ -129,11 +130,34 @@ class NativeTrainer:
             raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay}")
         if zero_stage and self.ema_decay > 0:
             raise ValueError("the weight EMA is not sharded; use zero_stage=0 with ema_decay > 0")
+        # debug mode synchronizes after every kernel, which graph capture forbids; per-phase
+        # profiling (DBX_PROFILE=phases: hipEvent timers + roctx ranges) needs eager phases too
+        self.phase_timer = PhaseTimer() if "phases" in os.environ.get("DBX_PROFILE", "").split(",") else None
+        self.use_graphs = (use_graphs and device.type == "cuda" and not _debug.enabled()
+                           and self.phase_timer is None)
+        # segmented = per-segment graphs + side-stream bucket all-reduces. Always on for world > 1;
+        # segmented_graphs forces it at world 1 (with an initialised process group) so the
+        # RCCL + capture interplay can be rehearsed on a one-GPU box.
+        self.segmented = self.world > 1 or (cfg.segmented_graphs and dist.is_available() and dist.is_initialized())
+        # comm "native": the DP bucket all-reduces go through the framework's own RCCL communicator
+        # (parallel/comm.py), and the whole step -- backward segments, forked all-reduces, join,
+        # optimizer -- is captured as ONE graph instead of per-segment graphs with eager c10d
+        # collectives between replays (ZeRO's reduce-scatter / all-gather included)
+        # (RCCL process groups, or a one-rank group: under gloo several ranks share one GPU in the
+        # one-box tests, and an RCCL communicator would refuse the duplicate device)
+        self.ncomm = None
+        if self.segmented and device.type == "cuda" and (self.world == 1 or dist.get_backend(process_group) == "nccl"):
+            from ..parallel.comm import native_comm_requested, open_verified_comm
+            if native_comm_requested(cfg):
+                self.ncomm = open_verified_comm(process_group, device)
+        context = ScheduleContext(cuda=device.type == "cuda", segmented=bool(self.segmented),
+                                  native_comm=self.ncomm is not None, use_graphs=self.use_graphs)
         # ZeRO: segment groups aligned to 16 x world elements (equal per-rank parts) and a flat bf16
         # parameter copy (the all-gather target the weight preparation reads)
         self.prog = ResNetProgram(model, batch, image_hw, device, src_hw=src_hw, mean=mean, std=std,
                                   param_align=16 * self.world if zero_stage else 16, param16=bool(zero_stage),
-                                  engine=cfg, src_ragged=src_ragged, resample=resample, eval_resample=eval_resample)
+                                  engine=cfg, src_ragged=src_ragged, resample=resample, eval_resample=eval_resample,
+                                  context=context)
         self.prog.build_backward()
         self.opt = optim
         self.smoothing = label_smoothing
@@ -198,31 +222,9 @@ class NativeTrainer:
         self.micro = 0  # position inside the window: calls to step() since the last boundary
         self.acc = torch.zeros(n, device=device) if self.k > 1 else None
         self.micro_graphs: List[Optional[torch.cuda.CUDAGraph]] = []
-        # debug mode synchronizes after every kernel, which graph capture forbids; per-phase
-        # profiling (DBX_PROFILE=phases: hipEvent timers + roctx ranges) needs eager phases too
-        self.phase_timer = PhaseTimer() if "phases" in os.environ.get("DBX_PROFILE", "").split(",") else None
-        self.use_graphs = (use_graphs and device.type == "cuda" and not _debug.enabled()
-                           and self.phase_timer is None)
         self.graphs: List[Optional[torch.cuda.CUDAGraph]] = []
         self.bucket_cap = int(bucket_cap_mb * (1 << 20) // 4)
         self.ar_dtype = allreduce_dtype
-        # segmented = per-segment graphs + side-stream bucket all-reduces. Always on for world > 1;
-        # segmented_graphs forces it at world 1 (with an initialised process group) so the
-        # RCCL + capture interplay can be rehearsed on a one-GPU box.
-        self.segmented = self.world > 1 or (cfg.segmented_graphs and dist.is_available() and dist.is_initialized())
-        self.comm_stream = (torch.cuda.Stream(device=device, priority=-1)
-                            if self.segmented and device.type == "cuda" else None)
-        # comm "native": the DP bucket all-reduces go through the framework's own RCCL communicator
-        # (parallel/comm.py) on the comm stream, and the whole step -- backward segments, forked
-        # all-reduces, join, optimizer -- is captured as ONE graph instead of per-segment graphs
-        # with eager c10d collectives between replays (ZeRO's reduce-scatter / all-gather included)
-        # (RCCL process groups, or a one-rank group: under gloo several ranks share one GPU in the
-        # one-box tests, and an RCCL communicator would refuse the duplicate device)
-        self.ncomm = None
-        if self.segmented and device.type == "cuda" and (self.world == 1 or dist.get_backend(process_group) == "nccl"):
-            from ..parallel.comm import native_comm_requested, open_verified_comm
-            if native_comm_requested(cfg):
-                self.ncomm = open_verified_comm(process_group, device)
         # comm_loopback W (test aid, world 1, DP): the framework communicator's all-reduce scales
         # by W in place -- the sum of W identical replicas -- and the update divides by W, so an
         # ordering bug of the one-graph step (a bucket all-reduced before its gradients are final:
@@ -239,67 +241,11 @@ class NativeTrainer:
                 self.loopback = self.ncomm.loopback = lb
             if direct_enabled(cfg) and zero_stage == 0 and self.world > 1 and self.ncomm.enable_direct(self.prog.grad):
                 self.grad_collectives += " + direct xGMI two-shot (small ranges)"
-        # Weight gradients next to the per-segment collectives. In the ONE-graph step (framework
-        # communicator) the batched side stream (one fork per backward segment, joined one segment
-        # later: overlap_wgrad 2) stays on with LATE posts: segment k's
-        # gradient range is final only after segment k+1 joins it, so its all-reduce / reduce-scatter
-        # is issued after phase k+1 (the last phase posts the last two ranges). Per-segment graphs
-        # (c10d collectives between replays) cannot carry a fork across a graph boundary (a capture
-        # must end joined), so there -- and with seg_side off -- the round-3 layout stays: weight
-        # gradients in order on the main stream, every range posted right after its own phase
-        # (per-gradient forks next to the comm stream cost more than they overlapped:
-        # profiles/r2s2_multirank/).
-        # The per-block layout (the single-GPU default: one side fork per residual block, lazy joins)
-        # keeps its schedule in the one-graph step (multirank_layout "block"): every weight gradient of
-        # segment k is queued on the side stream by the end of phase k, so the segment's collective is
-        # posted on that same stream right behind its last block batch -- in order, no late post -- and
-        # only the ranges whose last gradients run on the main stream in a later phase (layer1's
-        # block_tail_main gradients, computed after the stem backward) move to the last phase's post.
-        self.block_posts = bool(self.segmented and getattr(self.prog, "side_block_default", False)
-                                and cfg.multirank_layout == "block" and self.ncomm is not None
-                                and cfg.comm_side and device.type == "cuda")
-        if self.segmented and getattr(self.prog, "side_block_default", False) and not self.block_posts:
-            # the batched side stream with late posts (round 5's multi-rank layout; the c10d
-            # per-segment graphs can carry no fork across a graph boundary)
-            p, pol = self.prog, cfg.policy
-            p.side_block, p.side_batch = False, True
-            p.side_defer = cfg.side_defer if cfg.side_defer is not None else pol.small(p.fwd_flops)
-            p.lazy_join = cfg.lazy_join if cfg.lazy_join is not None else pol.tiny(p.fwd_flops)
-            p.stem_wg_main = cfg.stem_wg_main if cfg.stem_wg_main is not None else pol.small(p.fwd_flops)
-            # (with its collectives on the side stream the batched layout keeps the 64-CU reservation:
-            # world-1 RCCL one-graph step with a real collective kernel, headline +0.5-1.1 % over 128,
-            # TinyImageNet +0.1 %, profiles/r5_cu_reserve/sweep_late.txt)
-            if cfg.side_cu_reserve is None:
-                p.side_cu_reserve = 0 if pol.tiny(p.fwd_flops) else 64
-        seg_side = cfg.seg_side and (self.ncomm is not None or not self.use_graphs)
-        if self.segmented and cfg.overlap_wgrad is None and not seg_side:
-            self.prog.overlap_wgrad = False
-        self.late_posts = bool(self.segmented and device.type == "cuda" and seg_side and self.prog.overlap_wgrad
-                               and self.prog.side_batch)
-        if self.segmented and not self.late_posts:
-            # per-segment collectives right after their own phase need each segment's weight gradients
-            # final at its end: no batched side stream (it joins a segment late)
-            self.prog.side_batch = False
-        if self.segmented and not cfg.comm_side:
-            self.prog.lazy_join = False  # (a separate comm stream orders after the main stream's joins)
-        # comm_side (default on): in the one-graph step the collectives run on the weight-gradient
-        # side stream itself (behind the batch that finished their range) instead of a third stream.
-        # Under DEBUG_HIP_FORCE_GRAPH_QUEUES=2 a separate comm branch took the graph's second hardware
-        # queue and pushed the weight-gradient branch onto the main chain's queue: with a real
-        # collective in the graph (world-1 comm_loopback=2) TinyImageNet fell from 97.9k to 85.5k
-        # img/s and the headline by 1.2 % (profiles/r5_comm_queue/). The joins then wait on an event
-        # behind each batch, not on the collectives queued after it.
-        self.comm_side = bool(self.ncomm is not None and (self.late_posts or self.block_posts)
-                              and device.type == "cuda" and cfg.comm_side)
-        if self.comm_side:
-            self.comm_stream = self.prog.side_stream()
-            self.prog.event_joins = True
-            if cfg.side_defer is None:
-                self.prog.side_defer = True  # (the side branch then keeps its own hardware queue)
-        if self.segmented and ((self.prog.side_block and not self.block_posts) or not self.comm_side):
-            # collectives posted per segment need that segment's weight gradients joined at its end
-            # (lazy joins only where the collectives ride the side stream behind the batches)
-            self.prog.lazy_join = False
+        # where the collectives are posted and on which stream: the schedule's (engine/schedule.py)
+        sched = self.prog.sched
+        self.block_posts, self.late_posts, self.comm_side = sched.block_posts, sched.late_posts, sched.comm_side
+        self.comm_stream = (self.prog.side_stream() if sched.comm_side
+                            else torch.cuda.Stream(device=device, priority=-1) if sched.separate_comm_stream else None)
         self.flip = None
         self.seg_ranges = self._segment_ranges()
         self.zero = None
@@ -465,14 +411,14 @@ class NativeTrainer:
         for (name, fn), rg in zip(segs[1:], self.seg_ranges[1:]):
             phases.append((name, fn, rg))
         if self.segmented and self.late_posts:
-            # batched side stream: phase k completes segment k-1's weight gradients (see __init__)
+            # batched side stream: phase k completes segment k-1's weight gradients (late_posts, engine/schedule.py)
             rgs = [ph[2] for ph in phases]
             shifted = [None] + rgs[:-1]
             shifted[-1] = [r for r in (rgs[-2], rgs[-1]) if r is not None] if len(rgs) > 1 else rgs[-1]
             phases = [(n, fn, post) for (n, fn, _), post in zip(phases, shifted)]
         elif self.segmented and self.block_posts:
             # per-block layout: each range at its own phase's end, layer1's with the stem's when its last
-            # block's tail gradients run on the main stream after the stem backward (see __init__)
+            # block's tail gradients run on the main stream after the stem backward (block_posts, engine/schedule.py)
             if self.prog.block_tail_main > 0 and len(phases) > 1:
                 rgs = [ph[2] for ph in phases]
                 shifted = rgs[:-2] + [None, [r for r in (rgs[-2], rgs[-1]) if r is not None]]

@@ -25,6 +25,7 @@ Supported module trees: ``models.ResNet`` (BasicBlock / Bottleneck, any in_chann
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 import os
 from dataclasses import dataclass, field
@@ -36,6 +37,7 @@ import torch.nn as nn
 from ..engine_config import EngineConfig
 from ..models.resnet import BasicBlock, Bottleneck, CifarBlock, CifarResNet18, ResNet
 from ..ops import kernels as K
+from .schedule import ScheduleContext, StepSchedule, resolve_schedule
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -168,7 +170,7 @@ class ResNetProgram:
                  src_hw: Optional[Tuple[int, int]] = None, mean=None, std=None, param_align: int = 16,
                  param16: bool = False, engine: Optional[EngineConfig] = None,
                  src_ragged: Optional[Tuple[int, int]] = None, resample: Optional[str] = None,
-                 eval_resample: Optional[str] = None):
+                 eval_resample: Optional[str] = None, context: Optional[ScheduleContext] = None):
         """``image_hw``: network input size; ``src_hw``: size of the uint8 images handed in
         (crop/resize to image_hw happens on the GPU, ``augment_u8``); default = image_hw.
         ``src_ragged = (max_h, max_w)`` instead of ``src_hw``: the images handed in have sizes of their own, up to
@@ -182,8 +184,9 @@ class ResNetProgram:
         elements (ZeRO: 16 x world, so a segment splits into equal per-rank parts); ``param16``:
         keep a flat bf16 copy of the parameters (``self.param16``, ZeRO's all-gather target) and
         derive the compute weights from it instead of from the fp32 master. ``engine``: the schedule /
-        fusion switches (default ``EngineConfig.current()``; its ``None`` fields are resolved here by
-        the step-size policy)."""
+        fusion switches (default ``EngineConfig.current()``); ``context``: what the caller adds to the
+        single-GPU step (per-segment collectives, ...). ``engine/schedule.py`` resolves the two into
+        ``self.sched``, whose fields are also attributes of the program."""
         if not supports(model):
             raise TypeError(f"ResNetProgram does not support {type(model).__name__}")
         self.model = model
@@ -203,15 +206,6 @@ class ResNetProgram:
         self.dev = device
         self.in_ch = model.conv1.in_channels
         self.cfg = cfg = engine if engine is not None else EngineConfig.current()
-        pol = cfg.policy
-        ow = cfg.overlap_wgrad
-        # weight gradients on a side stream (overlap_wgrad None / 2: batched, one fork per backward
-        # segment -- see self.side_batch; "1": one fork per weight gradient; "0": in order on the main
-        # stream). Per-gradient forks cost more than they overlap on launch-bound steps (ResNet-18 CIFAR
-        # b256 189k img/s vs 222k in order) while one fork per segment wins at every size: CIFAR
-        # 229-230k, TinyImageNet 95.3-95.5k vs 90.6-91.5k, headline 16.07-16.15k vs 15.94-15.99k
-        # (profiles/r3s2_batched/)
-        self.overlap_wgrad = ow != 0
         # (the in-launch split-K reduce and the producer-side BN finalize (K.BnFin) measured slower than
         # the launches they remove on all three presets and were removed in round 6: profiles/r3s2_fuse_ab/;
         # the finalize re-measured after the round-6 changes: -4 % to -8 %, profiles/r6_fuse_fin/)
@@ -224,15 +218,8 @@ class ResNetProgram:
         self.pool_reduce = cfg.pool_reduce
         # BN-backward apply of a 1x1 conv's output BN computed in that conv's dgrad prologue
         self.fuse_bwd_apply = cfg.fuse_bwd_apply
-        # ... only for large operands: folding orders the wgrad after the dgrad (no overlap), which
-        # costs more than the saved pass when the kernels are too small to fill the GPU
-        self.fold_min = cfg.fold_min_elems if cfg.fold_min_elems is not None else 1 << 25
-        # ... and only where the dgrad's output channels (N) are at most this multiple of its
-        # reduction channels: every N tile of a folded dgrad re-reads and re-applies the operand
-        # (default 1: the bottleneck conv1 dgrads, N = 4K, stay unfolded -- 14.39-14.41k vs
-        # 14.22-14.27k img/s folded, ResNet-50 b1024, profiles/r2s3_fold/fold_ratio_ab.txt)
-        self.fold_max_ratio = cfg.fold_max_ratio if cfg.fold_max_ratio is not None else 1.0
-        # ... except at feature maps >= this size (the ratio limit is about the N-tile repeats of
+        # ... where the schedule's fold_min / fold_max_ratio allow, and at any ratio on feature maps >= this
+        # size (the ratio limit is about the N-tile repeats of
         # the operand prologue: at 56x56 the conv1 dgrads have only 1-2 N tiles; 15.19k / 15.21k vs
         # 15.17k / 15.13k img/s with the limit everywhere, profiles/r2s3_fold/fold_ratio_ab.txt)
         self.fold_ratio_min_hw = cfg.fold_ratio_min_hw
@@ -250,76 +237,23 @@ class ResNetProgram:
         # block's acts buffer, which backward needs anyway) and runs the conv without a prologue
         # (the same for the bottleneck's 1x1 conv3 measured -0.3 %: profiles/r3s2_hipenv/fast_mat1_ab.txt)
         self.fast_mat = cfg.fast_mat
+        # the downsample conv's forward beside conv2 / conv3 on the side stream: +0.24 % on the headline
+        # over five interleaved rounds, TinyImageNet neutral alone and +0.67 % with its block tail of one,
+        # CIFAR +0.6 % (profiles/r5_side_defer/ds_fwd.txt, block_tail.txt, cifar_late.txt)
+        self.ds_fwd_side = cfg.ds_fwd_side
         self._wstream = None
         self._side_pending = False
-        # overlap_wgrad 2: the side stream forks once per backward segment (batched) instead
-        # of once per weight gradient. Callers that need every segment's gradients final at its end
-        # (per-segment all-reduces: NativeTrainer / native_module at world > 1) turn it off.
-        self.side_batch = ow in (None, 2) and not self.fuse_stem_bwd  # (shares self.ws)
-        # 3: one fork per residual block (after its data gradients), every segment joined at its end:
-        # overlap that keeps segment-final gradients (the per-segment all-reduces at world > 1)
-        self.side_block = ow == 3 and not self.fuse_stem_bwd
         self._side_q = []
         self.param_align = max(16, int(param_align))
         self._want_param16 = param16
         self._build_layers()
-        # consumer-side forward BN finalize (K.conv_fwd fin_in): each workgroup of the
-        # consuming conv re-reads the statistics shards (2 x NSHARD x C doubles). Off: measured slower
-        # than the finalize launch it removes even on the launch-bound CIFAR step (212-214k vs 222k
-        # img/s; TinyImageNet 87.6k vs 89.5-89.9k, profiles/r3s2_finin/)
-        fl = self.fwd_conv_flops()
-        self.fwd_flops = fl
-        self.fin_in = bool(cfg.fin_in)
-        # Launch-bound small steps (< 0.5 TFLOP of forward conv work: the CIFAR / TinyImageNet presets)
-        # keep 4 statistics shards per BN instead of NSHARD, which makes the consumer-side forward
-        # finalize cheap enough to replace the bn_finalize launches: CIFAR 233.7-236.6k vs 229.1-231.0k,
-        # TinyImageNet 96.9-97.1k vs 95.4-96.0k img/s; the b1024 headline keeps NSHARD and standalone
-        # finalizes (16.14k with them vs 16.38-16.40k; profiles/r4_s6/, r4_s7/). nshard / fin_in set
-        # explicitly win.
-        self.small_step = pol.small(fl)
-        self.nshard = cfg.nshard if cfg.nshard is not None else (4 if self.small_step else K.NSHARD)
-        # (round 6: only the launch-bound CIFAR class keeps it; the TinyImageNet class runs the finalize
-        # launches again after the round-5/6 schedule changes: 105,548 / 105,605 vs 105,038 / 104,844
-        # img/s, profiles/r6_tiny_fin/)
-        if pol.tiny(fl) and cfg.fin_in is None:
-            self.fin_in = True
-        # consumer-side backward finalize: a BN-backward apply pass computes its coefficients from the
-        # moment shards itself (K.bn_bwd_apply fin=) instead of a bn_bwd_coeff launch in front of it
-        # (on by default for the small steps with 4-shard slabs: CIFAR 238.2-238.6k vs 233.7k img/s
-        # without it; at NSHARD = 32 every block of an apply would re-read 64 doubles per channel:
-        # profiles/r4_s7/); at 50-500 GFLOP (TinyImageNet) only for BNs of <= 512 channels: 95.7-95.9k vs 95.5k img/s
-        # (all widths 94.7k: an apply that finalizes in-launch is capped near C x 512 channel-finalizes,
-        # few blocks at 2048); CIFAR keeps every width (253.1-254.0k vs 251.6-252.5k at <= 256):
-        # profiles/r4_s18/. coeff_in_maxc overrides the width limit (0: none).
-        # by default the side stream forks once per residual BLOCK (overlap_wgrad 3; first from 50
-        # GFLOP of forward conv work up, TinyImageNet and ImageNet) -- with the deferred launch and lazy joins below
-        # that fills the windows where the batched side stream waited for its next fork: headline
-        # 16,755-16,865 vs 16,709-16,731, TinyImageNet 100.4-100.8k vs 99.4k img/s (CIFAR neutral at
-        # first): profiles/r5_side_defer/mode3.txt. The multi-rank trainer puts the batched layout back
-        # (its collectives are posted per segment).
-        # (late in round 5, with the block tails on the main stream and the downsample forward on the side
-        # stream, the CIFAR class gains too: 267.4-267.8k vs 262.3-263.0k img/s, profiles/r5_side_defer/
-        # cifar_late.txt -- the per-block default now covers every step size)
-        self.side_block_default = ow is None and not self.fuse_stem_bwd and self.overlap_wgrad
-        if self.side_block_default:
-            self.side_block, self.side_batch = True, False
-        self.coeff_in = cfg.coeff_in if cfg.coeff_in is not None else (pol.small(fl) and self.nshard <= 4)
-        mc = cfg.coeff_in_maxc
-        self.coeff_in_maxc = (mc or None) if mc is not None else (None if pol.tiny(fl) else 512)
-        # split-K weight-gradient reductions of a side-stream batch deferred to two launches at its end
-        # (K.ReduceBatch; 19 reduce launches per CIFAR step): on for the smallest steps (< 50 GFLOP),
-        # CIFAR 252.7-253.8k vs 243.7-245.5k img/s; TinyImageNet loses (93.3-93.8k vs 95.4k: its
-        # larger slabs leave L2 before the batch-end reduce), profiles/r4_s12/
-        self.defer_reduce = cfg.defer_reduce if cfg.defer_reduce is not None else pol.tiny(fl)
+        self.fwd_flops = self.fwd_conv_flops()
+        # the step's schedule: resolved once, here; nothing assigns its attributes afterwards
+        self._set_schedule(resolve_schedule(cfg, self.fwd_flops,
+                                            context or ScheduleContext(cuda=device.type == "cuda")))
+        self._main_tail, self._join_evt, self._pending_side = [], None, []
         self.wred_arena = torch.empty(0, device=device, dtype=torch.float32)
         self._wred_off = 0
-        if not self.overlap_wgrad:
-            # without the side stream folding costs no overlap: fold every BN-backward apply it can
-            # (unless set explicitly) -- CIFAR b256 193.7k vs 189.5k img/s with overlap (r3s2_knobs)
-            if cfg.fold_min_elems is None:
-                self.fold_min = 0
-            if cfg.fold_max_ratio is None:
-                self.fold_max_ratio = 8.0
         # stochastic depth (enable_drop_path): the gates, the gated BNs' effective parameters, the launch tables
         self.drop_gates = self.drop_eff = self._gate_fwd = None
         self.drop_blocks: List[int] = []
@@ -333,6 +267,16 @@ class ResNetProgram:
         self.training = True
         self.eval_ema = False  # evaluate from the trainer's weight EMA (NativeTrainer.evaluate_batch)
         self._skip_eval_coeff = False  # forward(bn_coeffs=False): the eval coefficients are in place already
+
+    def _set_schedule(self, sched: StepSchedule) -> None:
+        self.sched = sched
+        for f in dataclasses.fields(sched):
+            setattr(self, f.name, getattr(sched, f.name))
+
+    def replace_schedule(self, **changes) -> None:
+        """Test hook: run the next steps under ``dataclasses.replace(self.sched, **changes)``. Only for
+        fields the buffers do not depend on (``overlap_wgrad=False``: the same step without the side stream)."""
+        self._set_schedule(dataclasses.replace(self.sched, **changes))
 
     # ----------------------------------------------------------------------------------
     # construction
@@ -592,66 +536,12 @@ class ResNetProgram:
             wsmax = max(wsmax, cv.OC * ktot)
         # split-K wgrad workspace: up to 64 splits of the largest layer, >= 64 MiB
         self.ws = torch.empty(max(64 * wsmax, 16 << 20), device=dev, dtype=torch.float32)
-        # The step's exposed end (tools/step_timeline.py): after the last data gradient only the side
-        # stream's last batch (layer1's weight gradients) and the stem weight gradient behind it run.
-        # Small steps (< 0.5 TFLOP of forward conv work) run the stem weight gradient on the main stream
-        # beside that batch (stem_wg_main; CIFAR 257.0-257.6k vs 252.1-253.8k, TinyImageNet 96.7-96.8k
-        # vs 96.0-96.1k img/s; the b1024 headline loses 0.3 %: 16.48-16.49k vs 16.53-16.55k), and the
-        # TinyImageNet class (50-500 GFLOP) also moves the batch's last two gradients to the main
-        # stream's end (tail_main, their own workspace of ws's size: the same split depths, the same
-        # bits): 97.5-97.8k img/s; CIFAR loses with it (profiles/r5_tail/)
-        fl = self.fwd_flops
-        cfg, pol = self.cfg, self.cfg.policy
-        # side_defer: launch each side batch after the main stream's next kernel (see _flush_side).
-        # Default: on for the small steps (< 0.5 TFLOP of forward conv work: CIFAR +0.7 %, TinyImageNet
-        # neutral), off for the b1024 headline (-0.4 % / neutral); the multi-rank one-graph step turns it
-        # on (its collectives ride the side stream: TinyImageNet +2.8 %, CIFAR +5 %, profiles/r5_side_defer/)
-        self.side_defer = cfg.side_defer if cfg.side_defer is not None else (pol.small(fl) or self.side_block)
-        # side_cu_reserve: side-stream weight gradients sized to one round over all but N CUs, so
-        # the main chain's small kernels find a CU (the BN-backward coefficient launches took 4.9 us alone
-        # and 26.5 us beside the weight gradients); default 128 from the TinyImageNet class up (64: headline
-        # +0.8 %, TinyImageNet +0.6-0.9 %; re-swept with the per-block forks and main-stream tails, 128 over
-        # 64: TinyImageNet +1.8 %, headline +0.4 %; 160+ loses), 0 for the CIFAR class (64: -0.4 %, 128:
-        # -1 %): profiles/r5_cu_reserve/
-        self.side_cu_reserve = (cfg.side_cu_reserve if cfg.side_cu_reserve is not None
-                                else (0 if pol.tiny(fl) else 128))
-        # (with the per-block forks from 500 GFLOP up, together with two of the last block's weight
-        # gradients: headline +0.38 % over five interleaved rounds, profiles/r5_side_defer/block_tail.txt)
-        self.stem_wg_main = cfg.stem_wg_main if cfg.stem_wg_main is not None else (pol.small(fl) or self.side_block)
-        # (with the deferred launch the TinyImageNet class moves three: 99.7-100.4k vs 99.0-99.6k img/s)
-        self.tail_main = (cfg.tail_main if cfg.tail_main is not None
-                          else ((3 if self.side_defer else 2) if pol.mid(fl) else 0))
-        # the fused conv3 backward's persistent grid spans only this many CUs, so the side stream's weight
-        # gradients keep theirs (dwf_cus; 0 = all): TinyImageNet class 128 (+0.3 %), the headline
-        # loses with any span (-0.9 % at 192), profiles/r5_side_defer/tiny_knobs_late.txt
-        self.dwf_cus = cfg.dwf_cus if cfg.dwf_cus is not None else (128 if pol.mid(fl) else 0)
-        # the same as tail_main for the per-block side forks (overlap_wgrad 3): the last block's
-        # last N weight gradients (TinyImageNet at the 128-CU reservation: 2 over 1 +0.4 % in five of five
-        # interleaved rounds; headline +0.38 % with the stem's, profiles/r5_side_defer/block_tail.txt)
-        self.block_tail_main = cfg.block_tail_main
-        self._main_tail = []
-        self._join_evt = None
-        # set by the multi-rank trainer when its collectives share the side stream (comm_side):
-        # every segment join then waits for the event behind the segment's batch, not for the
-        # collectives queued behind it on the same stream (the final join waits for everything)
-        self.event_joins = False
-        # the downsample conv's forward beside conv2 / conv3 on the side stream: +0.24 % on the headline
-        # over five interleaved rounds, TinyImageNet neutral alone and +0.67 % with its block tail of one,
-        # CIFAR +0.6 % (profiles/r5_side_defer/ds_fwd.txt, block_tail.txt, cifar_late.txt)
-        self.ds_fwd_side = cfg.ds_fwd_side
-        # lazy_join: no intermediate joins of the batched side stream -- every side batch reads only
-        # its own segment's per-block buffers (never reused within a step) and the workspaces of the main
-        # stream's weight gradients are separate, so only the final join (before the optimizer) orders
-        # the two; not with collectives on their own stream (they wait on the main stream at the joins)
-        # (default: the CIFAR class, < 50 GFLOP of forward conv work, +1.2 %; TinyImageNet -0.3 %, the
-        # headline -0.5 %: profiles/r5_side_defer/lazy_join.txt)
-        self.lazy_join = cfg.lazy_join if cfg.lazy_join is not None else (pol.tiny(fl) or self.side_block)
-        self._pending_side = []
         # the stem weight gradient's own slabs when it runs on the main stream (its split count depends
         # on the grid, not on the workspace capacity)
         self.ws_stem = (torch.empty(40 << 20, device=dev, dtype=torch.float32)
                         if dev.type == "cuda" and self.stem_wg_main else self.ws)
-        # (not tied to the batched layout: the multi-rank trainer may switch a per-block default back to it)
+        # the workspace of the gradients moved to the main stream's tail (tail_main / block_tail_main:
+        # ws's size, so the same split depths and the same bits)
         self.ws_main = (torch.empty_like(self.ws) if ((self.tail_main > 0 or self.block_tail_main > 0)
                                                       and dev.type == "cuda"
                                                        and self.overlap_wgrad) else self.ws)
@@ -1599,7 +1489,7 @@ class ResNetProgram:
         else:
             K.maxpool_bwd(dp, self.parg, self.da0, K=self.pool_k, stride=self.pool_s, pad=self.pool_p)
             self._bn_bwd(sbn, self.da0, self.y0, self.dy0, self.N * st.OH * st.OW, K.MASK_Y)
-        # small steps (stem_wg_main, see __init__): with the batched side stream the stem weight gradient
+        # small steps (stem_wg_main, engine/schedule.py): with the batched side stream the stem weight gradient
         # runs on the MAIN stream right here, next to the side stream's last batch (layer1's weight
         # gradients, forked at layer1's end) instead of queued behind it; its slabs live in ws_stem
         on_main = ((self.side_batch or self.side_block) and self.dev.type == "cuda" and self.overlap_wgrad

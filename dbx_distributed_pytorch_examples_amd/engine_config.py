@@ -6,6 +6,8 @@ accepted by ``config.from_deepspeed``); the native engine adds the step schedule
 training step. Each field's default is the measured winner (the profile directory that measured it is
 named next to the field); ``None`` means "decided by the step-size policy" -- :class:`StepPolicy`
 names the forward-conv-FLOP classes those decisions switch on instead of literal thresholds.
+``engine/schedule.py`` (``resolve_schedule``) is the single place where the ``None`` of a schedule
+field is resolved, from this config, the step size and what the trainer adds (per-segment collectives).
 
 Where the engine reads it: ``EngineConfig.current()`` -- the process default, overridable for A/B runs
 through ONE environment variable::
@@ -47,10 +49,10 @@ class StepPolicy:
 
 @dataclass
 class EngineConfig:
-    # ---- weight-gradient overlap / step schedule (engine/program.py, engine/native_trainer.py) ----
+    # ---- weight-gradient overlap / step schedule (every None here: engine/schedule.py resolve_schedule) ----
     # side stream for weight gradients: 0 in order, 1 one fork per gradient, 2 one fork per backward
-    # segment, 3 one fork per residual block; None: 3 (r5_side_defer/mode3.txt), the multi-rank
-    # one-graph step keeps 2 with late collective posts
+    # segment, 3 one fork per residual block; None: 3 (r5_side_defer/mode3.txt), which the multi-rank
+    # one-graph step keeps (multirank_layout "block") or trades for 2 with late collective posts ("batch")
     overlap_wgrad: Optional[int] = None
     # launch each side batch after the main chain's next kernel (separate hardware queues);
     # None: small steps and the per-block layout (r5_side_defer/)

@@ -46,8 +46,8 @@ def build_native_step(args, info):
                   "ddp": (f"flat-bucket {'RCCL' if info.backend == 'nccl' else info.backend} all-reduce, "
                           f"{tr.bucket_cap * 4 >> 20} MiB chunks, "
                           f"{str(ar_dtype).split('.')[-1]}, overlapped per backward segment"
-                          + (" (framework RCCL communicator, whole step one HIP graph, weight-gradient side stream "
-                             "with late posts)" if tr.ncomm is not None else " (c10d between per-segment graphs)"))
+                          + (" (framework RCCL communicator, whole step one HIP graph; " if tr.ncomm is not None
+                             else " (c10d between per-segment graphs; ") + tr.prog.sched.describe() + ")")
                   + (f"; collectives: {tr.grad_collectives}" if tr.world > 1 else "")
                   if tr.world > 1 or getattr(tr, "segmented", False) else "none",
                   "kernels": "dbx HIP (conv implicit-GEMM MFMA + fused BN/ReLU/pool/CE/SGD)"}

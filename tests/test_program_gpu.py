@@ -170,7 +170,7 @@ def test_program_trains_and_graph_replay():
     t1 = NativeTrainer(m1, batch, (size, size), dev, optim=OptimConfig(lr=0.05), use_graphs=True)
     t2 = NativeTrainer(m2, batch, (size, size), dev, optim=OptimConfig(lr=0.05), use_graphs=False)
     t3 = NativeTrainer(m3, batch, (size, size), dev, optim=OptimConfig(lr=0.05), use_graphs=False)
-    t3.prog.overlap_wgrad = False
+    t3.prog.replace_schedule(overlap_wgrad=False)
     g = torch.Generator().manual_seed(2)
     img = torch.randint(0, 256, (batch, size, size, 3), dtype=torch.uint8, generator=g).to(dev)
     lab = torch.randint(0, 10, (batch,), generator=g).to(dev)
