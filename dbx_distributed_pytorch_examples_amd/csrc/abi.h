@@ -161,5 +161,42 @@ struct GemmArgs {
   float* ws;             // split-K (splitk > 1): fp32 partials [splitk][M][N], summed in split order
   int splitk;            // K split over blockIdx.z (1: the tile loop writes C itself)
 };
+// Squeeze-and-excitation kernels (se_ops.hip). One table for all of them: Python packs it as 32 pointers followed
+// by 8 int32 (ops/kernels.py _se_launch), each kernel reads the fields it needs, the rest are null.
+// y: the raw output of the block's last conv [N][HW][C]; the [N][C] tables are per sample and channel.
+struct SeArgs {
+  const bf16* y;
+  const bf16* g;              // block-output gradient [N][HW][C], unmasked
+  const bf16* res;            // shortcut operand [N][HW][C] (res_mode 1: added as is, 2: res * rsc + rsh)
+  bf16* out;                  // se_tail: block output; se_bwd_apply: dy
+  bf16* gout;                 // se_bwd_apply: the masked block-output gradient
+  unsigned char* mbits;       // 1-bit ReLU mask of the block output (bn_apply's format)
+  const float* scale;         // last BN: forward scale / shift, batch mean / invstd, gamma / beta, [C] each
+  const float* shift;
+  const float* mean;
+  const float* invstd;
+  const float* gamma;
+  const float* beta;
+  const float* rsc;           // shortcut BN scale / shift (res_mode 2)
+  const float* rsh;
+  const float* coeff;         // [3][C] bn_bwd_coeff's k1, k2, k3
+  float* zsum;                // [N][C] sum over hw of y
+  float* gate;                // [N][C] fp32
+  float* A;                   // [N][C] sum over hw of the masked gradient gm
+  float* B;                   // [N][C] sum over hw of gm * xhat
+  float* dz;                  // [N][C] gradient of the squeezed mean
+  bf16* zq;                   // [N][C] bf16 squeezed mean (forward) / dpre2 (backward)
+  bf16* h;                    // [N][rd] bf16 relu(fc1) (forward: written, backward: read)
+  bf16* dpre1;                // [N][rd]
+  float* part;                // reductions with nsplit > 1: fp32 [nsplit][2][N][C] partial sums
+  const bf16* wa;             // excite: W1 [rd][C]; excite_bwd: W2 [C][rd]  (the GEMM with K = C)
+  const float* ba;            // excite: b1 [rd]
+  const bf16* wb;             // excite: W2 [C][rd]; excite_bwd: W1 [rd][C]  (the GEMM with K = rd)
+  const float* bb;            // excite: b2 [C]
+  double* bstats;             // excite_bwd: the last BN's backward moments [nshard][2][C] (sum du, sum du * xhat)
+  const void* rsv_[3];
+  int N, HW, C, rd, nsplit, nshard, res_mode, pad_;
+};
+static_assert(sizeof(SeArgs) == 32 * 8 + 8 * 4, "ops/kernels.py packs SeArgs as 32 pointers + 8 int32");
 
 }  // namespace dbx

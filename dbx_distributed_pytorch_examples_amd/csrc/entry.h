@@ -69,7 +69,10 @@ int dbx_maxpool_bwd(const bf16* dout, const unsigned char* arg, bf16* dx, int N,
 int dbx_pool_bn_bwd(const bf16* dpool, const unsigned char* arg, const bf16* y, const float* sc, const float* sh,
                     const float* c1, const float* c2, const float* c3, bf16* dy, double* stats, int nshard, int N,
                     int H, int W, int C, int P, int Q, int K, int stride, int pad, int apply, hipStream_t st);
-int dbx_avgpool_fwd(const bf16* x, bf16* out, int N, int HW, int C, hipStream_t st);
+// se_op != 0: the squeeze-and-excitation kernels instead -- forwards to dbx_se_op(se_op, se_args) below; x, out and
+// the sizes are then unread
+int dbx_avgpool_fwd(const bf16* x, bf16* out, int N, int HW, int C, hipStream_t st, int se_op,
+                    const dbx::SeArgs* se_args);
 int dbx_avgpool_bwd(const bf16* dout, bf16* dx, int N, int HW, int C, hipStream_t st);
 // the training loss: kind 0 = softmax cross-entropy, 1 = binary cross-entropy on the logits (target_thresh >= 0
 // binarises the targets, negative = none; sum_classes: the row loss is summed over the classes, not averaged)
@@ -137,6 +140,11 @@ int dbx_ta_apply_u8(const unsigned char* T, bf16* out, const int* ops, const uns
 // reaches it through ta_apply_u8's binding: a non-null T_out there forwards here (out and the mixing arguments unread)
 int dbx_ta_stage_u8(const unsigned char* T_in, unsigned char* T_out, int* hist, const int* ops,
                     const unsigned char* lut, const int* tmean, int N, int Ho, int Wo, hipStream_t st);
+
+// ---- squeeze-and-excitation (se_ops.hip) --------------------------------------------------------------------------
+// op 1 se_squeeze, 2 se_excite, 3 se_tail, 4 se_bwd_reduce, 5 se_excite_bwd, 6 se_bwd_apply on the fields of *args (a
+// HOST struct, abi.h) that the op names. Python reaches it through avgpool_fwd's binding (a nonzero se_op there)
+int dbx_se_op(int op, const dbx::SeArgs* args, hipStream_t st);
 
 // ---- classifier head (head_ops.hip) -----------------------------------------------------------------------------
 int dbx_small_gemm(int ta, int tb, int out_f32, int drop, const dbx::GemmArgs* args, hipStream_t st);

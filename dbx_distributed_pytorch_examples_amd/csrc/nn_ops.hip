@@ -1090,7 +1090,9 @@ extern "C" int dbx_pool_bn_bwd(const bf16* dpool, const unsigned char* arg, cons
                        N, H, W, C, P, Q, K, stride, pad);
   RET_LAST;
 }
-extern "C" int dbx_avgpool_fwd(const bf16* x, bf16* out, int N, int HW, int C, hipStream_t st) {
+extern "C" int dbx_avgpool_fwd(const bf16* x, bf16* out, int N, int HW, int C, hipStream_t st, int se_op,
+                               const dbx::SeArgs* se_args) {
+  if (se_op != 0) return se_args ? dbx_se_op(se_op, se_args, st) : -91;
   if (C % 8) return -1;
   hipLaunchKernelGGL(avgpool_fwd_kernel, dim3((C / 8 + 63) / 64, N), dim3(64), 0, st, x, out, N, HW, C);
   RET_LAST;

@@ -310,6 +310,9 @@ class NativeTrainer:
             pairs += [(mean, bn.mod.running_mean), (var, bn.mod.running_var)]
             # what an evaluation from the average hands bn_eval_coeff (program._bn_fwd)
             bn.ema_eval = (self.ema[bn.off_w:bn.off_w + bn.C], self.ema[bn.off_b:bn.off_b + bn.C], mean, var)
+        for se in p.ses:  # the gates' biases are read in fp32: an evaluation from the average takes its own views
+            o1, o2 = se.off["fc1.bias"], se.off["fc2.bias"]
+            se.ema_b = (self.ema[o1:o1 + se.rd], self.ema[o2:o2 + se.C])
         p.bn_eval_table_ema = p.pack_bn_eval(ema=True)  # an evaluation pass from the average (eval_begin)
         self._ema_bn_desc = K.pack_ema_desc(pairs, dev)
         self._ema_bn_n, self._ema_bn_max = len(pairs), max(bn.C for bn in p.bns)

@@ -19,7 +19,8 @@ Parameters live in ONE flat fp32 master buffer (conv weights in KRSC order); the
 optimizer already holding them, stay valid; conv weights as channels_last views), so
 ``model.state_dict()`` / ``load_state_dict`` / checkpoint files keep torchvision layouts.
 
-Supported module trees: ``models.ResNet`` (BasicBlock / Bottleneck, any in_channels <= 4; Bottleneck also widened
+Supported module trees: ``models.ResNet`` (BasicBlock / Bottleneck, any in_channels <= 4, every block with or without
+a squeeze-and-excitation gate ``se``; Bottleneck also widened
 (Wide ResNet) or with a grouped 3x3 conv2 (ResNeXt: ``K.group_conv_supported``, 4 to 64 channels per group)) and
 ``models.CifarResNet18``; everything else trains through the autograd path (engine.autograd_step).
 """
@@ -35,7 +36,7 @@ import torch
 import torch.nn as nn
 
 from ..engine_config import EngineConfig
-from ..models.resnet import BasicBlock, Bottleneck, CifarBlock, CifarResNet18, ResNet
+from ..models.resnet import BasicBlock, Bottleneck, CifarBlock, CifarResNet18, ResNet, SEModule
 from ..ops import kernels as K
 from .schedule import ScheduleContext, StepSchedule, resolve_schedule
 
@@ -141,6 +142,24 @@ class BNL:
 
 
 @dataclass
+class SEL:
+    """A block's squeeze-and-excitation gate (models.SEModule; csrc/se_ops.hip)."""
+    name: str
+    mod: SEModule
+    C: int
+    rd: int
+    off: Dict[str, int] = field(default_factory=dict)   # master offsets of fc1.weight, fc1.bias, fc2.weight, fc2.bias
+    w1_16: Optional[torch.Tensor] = None   # [rd, C] / [C, rd] bf16 compute copies
+    w2_16: Optional[torch.Tensor] = None
+    b1: Optional[torch.Tensor] = None      # fp32 master views
+    b2: Optional[torch.Tensor] = None
+    ema_b: Optional[Tuple[torch.Tensor, torch.Tensor]] = None   # the biases' views of a trainer's weight EMA
+    grads: Dict[str, torch.Tensor] = field(default_factory=dict)   # fp32 views into the flat gradient
+    # per-sample tables: zsum, gate, A, B, dz fp32 [N, C]; zq, dpre2 bf16 [N, C]; h, dpre1 bf16 [N, rd]
+    tabs: Dict[str, torch.Tensor] = field(default_factory=dict)
+
+
+@dataclass
 class BlockL:
     kind: str                      # "bottleneck" | "basic"
     convs: List[ConvL]
@@ -161,6 +180,7 @@ class BlockL:
     dyd: Optional[torch.Tensor] = None
     dsbuf: Optional[torch.Tensor] = None
     dx: Optional[torch.Tensor] = None                       # grad wrt block input
+    se: Optional[SEL] = None                                # the gate on the last BN's output (SE-ResNet)
 
 
 class ResNetProgram:
@@ -293,6 +313,21 @@ class ResNetProgram:
         oh, ow = K.conv_out_hw(ih, iw, R, S, st, pad)
         return ConvL(name, mod, mod.in_channels, mod.out_channels, R, S, st, pad, ih, iw, oh, ow, stem, mod.groups)
 
+    @staticmethod
+    def _se(name: str, mod, C: int) -> SEL:
+        fc1, fc2 = getattr(mod, "fc1", None), getattr(mod, "fc2", None)
+        ok = (isinstance(mod, SEModule) and isinstance(fc1, nn.Conv2d) and isinstance(fc2, nn.Conv2d)
+              and fc1.kernel_size == (1, 1) and fc2.kernel_size == (1, 1) and fc1.bias is not None
+              and fc2.bias is not None and fc1.in_channels == C and fc2.out_channels == C
+              and fc1.out_channels == fc2.in_channels and fc1.groups == 1 and fc2.groups == 1)
+        if not ok:
+            raise TypeError(f"{name}: unsupported gate (a models.SEModule of {C} channels is expected)")
+        rd = fc1.out_channels
+        if not K.se_rd_supported(C, rd):
+            raise TypeError(f"{name}: the SE kernels take C % 64 == 0 and a squeezed width that is a multiple of 8 in "
+                            f"{K.SE_RD_MIN}..{K.SE_RD_MAX}, got C={C}, rd={rd}")
+        return SEL(name, mod, C, rd)
+
     def _build_layers(self):
         m = self.model
         self.stem = self._conv("conv1", m.conv1, self.H, self.W, stem=True)
@@ -343,6 +378,8 @@ class ResNetProgram:
                     dsb = BNL(f"{pre}.{dsn}.1", ds[1], ds[1].num_features)
                 last = convs[-1]
                 blk_l = BlockL(kind, convs, bns, dsc, dsb, (h, w, c), (last.OH, last.OW, last.OC))
+                if getattr(blk, "se", None) is not None:
+                    blk_l.se = self._se(f"{pre}.se", blk.se, last.OC)
                 self.blocks.append(blk_l)
                 h, w, c = last.OH, last.OW, last.OC
         self.feat_hw = (h, w)
@@ -351,6 +388,7 @@ class ResNetProgram:
         self.num_classes = m.fc.out_features
         self.convs: List[ConvL] = [self.stem] + [cv for b in self.blocks for cv in (b.convs + ([b.ds_conv] if b.ds_conv else []))]
         self.bns: List[BNL] = [self.stem_bn] + [bn for b in self.blocks for bn in (b.bns + ([b.ds_bn] if b.ds_bn else []))]
+        self.ses: List[SEL] = [b.se for b in self.blocks if b.se is not None]
         for cv in self.convs[1:]:
             if cv.IC % 64 or cv.OC % 64:
                 raise TypeError(f"{cv.name}: channels must be multiples of 64 for the HIP conv kernels")
@@ -370,9 +408,14 @@ class ResNetProgram:
                 if bn.name.startswith(pre) or (bn is self.stem_bn and "bn1." in pre):
                     entries.append(("bn_w", bn, "weight", bn.C))
                     entries.append(("bn_b", bn, "bias", bn.C))
+            for se in self.ses:  # a block's gate joins its stage: every backward segment stays one range
+                if se.name.startswith(pre):
+                    entries += [("se", se, "fc1.weight", se.rd * se.C), ("se", se, "fc1.bias", se.rd),
+                                ("se", se, "fc2.weight", se.rd * se.C), ("se", se, "fc2.bias", se.C)]
         entries.append(("fc_w", self.fc, "weight", self.fc.weight.numel()))
         entries.append(("fc_b", self.fc, "bias", self.fc.bias.numel()))
-        assert len(entries) == len(self.convs) + 2 * len(self.bns) + 2, "parameter grouping lost a tensor"
+        assert len(entries) == len(self.convs) + 2 * len(self.bns) + 4 * len(self.ses) + 2, \
+            "parameter grouping lost a tensor"
         # 16-element alignment of every tensor (vectorised kernels, 64-B bucket edges); every
         # backward segment's group (stem | layer1..4 | fc) starts on a multiple of param_align
         A = self.param_align
@@ -384,6 +427,7 @@ class ResNetProgram:
             for bn in self.bns:
                 if bn.name.startswith(pre) or (bn is self.stem_bn and "bn1." in pre):
                     group_of += [gi, gi]
+            group_of += [gi] * (4 * sum(se.name.startswith(pre) for se in self.ses))
         group_of += [len(groups), len(groups)]
         total = 0
         offs = []
@@ -432,6 +476,19 @@ class ResNetProgram:
                         # one int64 counter per BN, all views of self.nbt (one add per step)
                         nbt_vals.append(int(mod.num_batches_tracked))
                         nbt_mods.append(mod)
+                elif kind == "se":
+                    se: SEL = obj
+                    fc, what = attr.split(".")
+                    p = getattr(getattr(se.mod, fc), what)
+                    flat = self.master[off:off + n]
+                    flat.copy_(p.detach().reshape(-1).to(dev, torch.float32))
+                    _repoint(p, flat.view(p.shape))
+                    se.off[attr] = off
+                    se.grads[attr] = self.grad[off:off + n].view(p.shape[0], -1) if what == "weight" \
+                        else self.grad[off:off + n]
+                    if what == "bias":
+                        setattr(se, "b1" if fc == "fc1" else "b2", flat)
+                    self.param_ranges.append((f"{se.name}.{attr}", off, n))
                 else:
                     p = getattr(self.fc, attr)
                     flat = self.master[off:off + n]
@@ -461,6 +518,11 @@ class ResNetProgram:
                 n16 += cv.numel
             descs.append((cv.off, fwd_off, tr_off, cv.OC, cv.R * cv.S, cv.cpg))
             cv._w16_off, cv._wt16_off = fwd_off, tr_off
+        for se in self.ses:  # plain casts, like the fc weight
+            se._w16_off = (n16, n16 + se.rd * se.C)
+            descs.append((se.off["fc1.weight"], n16, -1, se.rd, 1, se.C))
+            descs.append((se.off["fc2.weight"], n16 + se.rd * se.C, -1, se.C, 1, se.rd))
+            n16 += 2 * se.rd * se.C
         fc_off = n16
         n16 += self.fc.weight.numel()
         descs.append((self.fc_w_off, fc_off, -1, self.num_classes, 1, self.fc.in_features))
@@ -481,6 +543,10 @@ class ResNetProgram:
             cv.w16 = self.w16buf[cv._w16_off:cv._w16_off + cv.numel].view(cv.OC, -1)
             if cv.groups == 1:
                 cv.wt16 = self.w16buf[cv._wt16_off:cv._wt16_off + cv.numel].view(cv.IC, -1)
+        for se in self.ses:
+            o1, o2 = se._w16_off
+            se.w1_16 = self.w16buf[o1:o1 + se.rd * se.C].view(se.rd, se.C)
+            se.w2_16 = self.w16buf[o2:o2 + se.rd * se.C].view(se.C, se.rd)
         self.fc_w16 = self.w16buf[fc_off:fc_off + self.fc.weight.numel()].view(self.num_classes, -1)
         self.fc_b16 = self.w16buf[fcb_off:fcb_off + self.num_classes]
         self._wdescs = descs  # + the per-step entries (_pack_step_descs, after the activations exist)
@@ -531,6 +597,19 @@ class ResNetProgram:
             # 1-bit ReLU mask of the block output (the next block's dgrad epilogue masks with it:
             # 1/16 of the bytes of re-reading the bf16 output)
             b.obits = torch.empty(N * oh * ow * oc // 8, device=dev, dtype=torch.uint8)
+        # SE blocks: the per-sample tables, one masked-gradient scratch buffer for all of them (a block's shortcut
+        # add is its last reader) and the partial sums of the split reductions
+        self.se_g = self.se_ws = None
+        if self.ses:
+            f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)  # noqa: E731
+            z16 = lambda *s: torch.zeros(*s, device=dev, dtype=bf)  # noqa: E731
+            for se in self.ses:
+                se.tabs = dict({k: f32(N, se.C) for k in ("zsum", "gate", "A", "B", "dz")}, zq=z16(N, se.C),
+                               dpre2=z16(N, se.C), h=z16(N, se.rd), dpre1=z16(N, se.rd))
+            seb = [b for b in self.blocks if b.se is not None]
+            self.se_g = E(max(b.out.numel() for b in seb))
+            self.se_ws = torch.empty(max(K.se_nsplit(b.out_shape[0] * b.out_shape[1]) * 2 * N * b.se.C for b in seb),
+                                     device=dev, dtype=torch.float32)
         for cv in self.convs:
             ktot = 256 if cv.stem else cv.R * cv.S * cv.cpg
             wsmax = max(wsmax, cv.OC * ktot)
@@ -773,6 +852,10 @@ class ResNetProgram:
         self.drop_blocks = [l for l, q in enumerate(probs) if q > 0.0]
         if not self.drop_blocks:
             return
+        if self.ses:  # (the scaled gamma / beta would feed the gated BN output to the squeeze)
+            self.drop_blocks = []
+            raise ValueError("enable_drop_path: stochastic depth scales a block's last BN, which a squeeze-and-excitation "
+                             "block reads before its gate; drop_path_rate > 0 is not built for models with SE blocks")
         dev = self.dev
         self.drop_gates = torch.ones(len(self.drop_blocks), device=dev, dtype=torch.float32)
         cpad = lambda c: (c + 3) // 4 * 4  # noqa: E731  (16-byte aligned rows: the vector path)
@@ -821,9 +904,13 @@ class ResNetProgram:
                 self._erase_ctr.add_(1)
 
     def bn_param_blocks(self) -> List[Tuple[int, int]]:
-        """Contiguous [lo, hi) blocks of the flat buffer holding BatchNorm affine parameters (read in
-        fp32 by the BN kernels), merged where adjacent."""
-        rs = sorted((o, o + (bn.C + 15) // 16 * 16) for bn in self.bns for o in (bn.off_w, bn.off_b))
+        """Contiguous [lo, hi) blocks of the flat buffer holding the parameters the kernels read in fp32
+        (BatchNorm affine parameters, SE biases), merged where adjacent."""
+        rs = [(o, o + (bn.C + 15) // 16 * 16) for bn in self.bns for o in (bn.off_w, bn.off_b)]
+        # (and the SE gates' biases, which the excite kernel reads from the master as well)
+        rs += [(se.off[k], se.off[k] + (n + 15) // 16 * 16) for se in self.ses
+               for k, n in (("fc1.bias", se.rd), ("fc2.bias", se.C))]
+        rs.sort()
         out: List[Tuple[int, int]] = []
         for lo, hi in rs:
             if out and out[-1][1] == lo:
@@ -937,17 +1024,18 @@ class ResNetProgram:
                 deferred = None
                 # (the fork follows conv1, whose tail prologue writes the block input; forking before
                 # conv1 where the input is already in memory measured neutral in round 5)
-                if i == 0 and ds_launch is not None and b.ds_conv is not None:
+                if i == 0 and ds_launch is not None and b.ds_conv is not None and b.se is None:
                     ds_launch[bi] = self._ds_fwd_on_side(b, x, N)
                 nxt = self.blocks[bi + 1] if bi + 1 < len(self.blocks) else None
                 c1 = nxt.convs[0] if nxt is not None else None
-                tail = (self.fuse_tail and c1 is not None
+                tail = (self.fuse_tail and c1 is not None and b.se is None
                         and K.tail_supported(b.out_shape[2], c1.R, c1.S, c1.stride, c1.pad))
                 if self._ff(b.bns[i]) is None:
                     if (tr and self.fin_in and i + 1 < len(b.convs) and not b.mat[i]
                             and b.bns[i].fin_f is not None):
                         deferred = b.bns[i]  # finalized by the next conv's prologue
-                    elif tr and self.fin_in and i + 1 == len(b.convs) and b.bns[i].fin_f is not None:
+                    elif (tr and self.fin_in and i + 1 == len(b.convs) and b.bns[i].fin_f is not None
+                          and b.se is None):
                         out_fin = b.bns[i].fin_f  # finalized by the block-output bn_apply / next conv1 below
                     else:
                         self._bn_fwd(b.bns[i], N * cv.OH * cv.OW)
@@ -961,7 +1049,7 @@ class ResNetProgram:
                     K.conv_fwd(x, dc.w16, b.yd, R=dc.R, S=dc.S, stride=dc.stride, pad=dc.pad,
                                stats=b.ds_bn.stats if tr else None, fin=self._ff(b.ds_bn))
                 if self._ff(b.ds_bn) is None:
-                    if tr and self.fin_in and b.ds_bn.fin_f is not None:
+                    if tr and self.fin_in and b.ds_bn.fin_f is not None and b.se is None:
                         res_fin = b.ds_bn.fin_f  # finalized by the block-output bn_apply / next conv1 below
                     elif side_ds is None:
                         self._bn_fwd(b.ds_bn, N * dc.OH * dc.OW)
@@ -971,7 +1059,17 @@ class ResNetProgram:
                 res, rsc, rsh = b.yd, b.ds_bn.scale, b.ds_bn.shift
             else:
                 res, rsc, rsh = x, None, None
-            if tail:
+            if b.se is not None:
+                # squeeze -> excite -> gated tail (csrc/se_ops.hip): both BNs were finalized standalone above, and
+                # the next block's conv1 reads b.out as a plain operand
+                se, t, hw = b.se, b.se.tabs, b.out_shape[0] * b.out_shape[1]
+                b1, b2 = se.ema_b if (not tr and self.eval_ema and se.ema_b is not None) else (se.b1, se.b2)
+                K.se_squeeze(b.ys[-1], t["zsum"], ws=self.se_ws)
+                K.se_excite(t["zsum"], last.scale, last.shift, hw, se.w1_16, b1, se.w2_16, b2, t["zq"], t["h"],
+                            t["gate"])
+                K.se_tail(b.ys[-1], last.scale, last.shift, t["gate"], b.out, res=res, res_scale=rsc, res_shift=rsh,
+                          mbits=b.obits if tr else None)
+            elif tail:
                 # b.out (+ its mask) is written by the next block's conv1 (which also finalizes the
                 # tail BNs deferred above)
                 pending = (b, res, rsc, rsh, out_fin, res_fin)
@@ -1278,7 +1376,9 @@ class ResNetProgram:
         pend, gin = None, None  # BN-backward apply deferred into the next dgrad's prologue
         ds_fold = None  # ... and the downsample BN's, into the downsample dgrad
         fuse3 = self._fuse3(b, last)  # conv3's BN-backward apply + dgrad + wgrad in one kernel
-        if last:
+        if b.se is not None:
+            g = self._bwd_se_tail(b, self.dlast if last else self.blocks[i + 1].dx)
+        elif last:
             # g = dlast * (out > 0) -> self.g_last ; tail BN reductions (and ds BN) from dlast
             K.bn_bwd_reduce(self.dlast, b.ys[-1], lbn.mean, lbn.invstd, lbn.bstats, mask_mode=K.MASK_OUT, mref=b.out)
             if b.ds_conv is not None:
@@ -1295,7 +1395,7 @@ class ResNetProgram:
         # backward finalizes still to run for the tail BNs (else finished by block i+1's conv1 dgrad
         # epilogue): run standalone before a consumer that reads the coefficients from memory, or
         # handed to the apply pass that consumes them (coeff_in)
-        todo = {} if last else ({id(lbn): (lbn, cnt_last)} if not self._fused_fin(lbn) else {})
+        todo = {} if last or b.se is not None else ({id(lbn): (lbn, cnt_last)} if not self._fused_fin(lbn) else {})
 
         def ready(bn):  # the coefficients are in memory before the next launch
             if id(bn) in todo:
@@ -1310,9 +1410,9 @@ class ResNetProgram:
 
         if b.ds_conv is not None:
             dc, dbn = b.ds_conv, b.ds_bn
-            if last or not self._fused_fin(dbn):
+            if last or b.se is not None or not self._fused_fin(dbn):
                 todo[id(dbn)] = (dbn, N * dc.OH * dc.OW)
-            if last:
+            if last or b.se is not None:  # (an SE block: g is the masked scratch gradient, nothing is folded)
                 K.bn_bwd_apply(g, b.yd, dbn.coeff, b.dyd, mask_mode=K.MASK_NONE, fin=fin_of(dbn))
             elif (fuse3 or self._fold(lc)) and self._fold(dc, dense=True):
                 # both tail BN applies folded into the dgrads of conv3 and of the downsample conv
@@ -1329,7 +1429,7 @@ class ResNetProgram:
             else:  # both tail BNs from one read of the block-output gradient
                 f1, f2 = fin_of(lbn), fin_of(dbn)
                 K.bn_bwd_apply2(g, b.ys[-1], lbn.coeff, b.dys[-1], b.yd, dbn.coeff, b.dyd, fin1=f1, fin2=f2)
-        elif not last:
+        elif not last and b.se is None:
             if fuse3 or self._fold(lc):  # folded into conv3's dgrad prologue (it stores dys[-1] for the wgrad)
                 ready(lbn)
                 pend = dict(bwd_y=b.ys[-1], bwd_coeff=lbn.coeff, dy_out=b.dys[-1])
@@ -1410,7 +1510,7 @@ class ResNetProgram:
         else:
             addsrc, sub = g, 1
         epi = None
-        if i > 0:
+        if i > 0 and self.blocks[i - 1].se is None:  # (an SE block takes the raw gradient: se_bwd_reduce masks it)
             pb = self.blocks[i - 1]
             epi = K.BNBwdEpilogue(K.MASK_OUT, pb.ys[-1], pb.bns[-1].mean, pb.bns[-1].invstd, pb.bns[-1].bstats,
                                   mbits=pb.obits,
@@ -1425,6 +1525,27 @@ class ResNetProgram:
                      addsrc=addsrc, add_sub=sub, epilogue=epi, **kw0)
         if kw0:
             self._wgrad(b.dys[0], x, c0.grad, self.ws, R=c0.R, S=c0.S, stride=c0.stride, pad=c0.pad)
+
+    def _bwd_se_tail(self, b: BlockL, g_raw: torch.Tensor) -> torch.Tensor:
+        """Backward of an SE block's tail (csrc/se_ops.hip) from the raw block-output gradient: the gate's parameter
+        gradients, dys[-1] of the last conv, the downsample BN's moments; returns the masked gradient (scratch)."""
+        N, se, t, lbn = self.N, b.se, b.se.tabs, b.bns[-1]
+        lc = b.convs[-1]
+        hw, y = lc.OH * lc.OW, b.ys[-1]
+        gm = self.se_g[:y.numel()].view(y.shape)
+        K.se_bwd_reduce(g_raw, b.obits, y, lbn.mean, lbn.invstd, t["A"], t["B"], ws=self.se_ws)
+        if b.ds_conv is not None:
+            K.bn_bwd_reduce(g_raw, b.yd, b.ds_bn.mean, b.ds_bn.invstd, b.ds_bn.bstats, mask_mode=K.MASK_OUT, mref=b.out)
+        K.se_excite_bwd(t["A"], t["B"], t["gate"], t["h"], t["zsum"], hw, lbn.gamma_t, lbn.beta_t, lbn.mean,
+                        lbn.invstd, se.w2_16, se.w1_16, t["dpre2"], t["dpre1"], t["dz"], lbn.bstats)
+        self._coeff(lbn, N * hw)
+        K.se_bwd_apply(g_raw, b.obits, y, t["gate"], t["dz"], lbn.coeff, b.dys[-1], gm)
+        # the gate's parameters, like the fc: dW = dpre^T x (fp32, into the flat gradient), db = column sums
+        K.small_gemm(t["dpre2"], t["h"], se.grads["fc2.weight"], ta=True, tb=True, M=se.C, N=se.rd, K=N)
+        K.colsum(t["dpre2"], se.grads["fc2.bias"])
+        K.small_gemm(t["dpre1"], t["zq"], se.grads["fc1.weight"], ta=True, tb=True, M=se.rd, N=se.C, K=N)
+        K.colsum(t["dpre1"], se.grads["fc1.bias"])
+        return gm
 
     def fwd_conv_flops(self) -> float:
         """FLOPs of the forward convolutions of one step (sizes the wgrad side-stream decision)."""
@@ -1450,7 +1571,7 @@ class ResNetProgram:
     def _fuse3(self, b: BlockL, last: bool) -> bool:
         """Run block b's conv3 backward through K.conv_dwfused (the 64 -> 256 conv3 of the 56x56
         stage: its weight-gradient accumulators fit a workgroup's registers)."""
-        if not self.fuse_dw or last or b.kind != "bottleneck":
+        if not self.fuse_dw or last or b.kind != "bottleneck" or b.se is not None:
             return False
         c3 = b.convs[-1]
         return ((c3.R, c3.S, c3.stride, c3.pad) == (1, 1, 1, 0) and c3.OH >= self.cfg.fuse_dw_min_hw

@@ -25,7 +25,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 __all__ = [
-    "BasicBlock", "Bottleneck", "ResNet", "resnet18", "resnet34", "resnet50",
+    "BasicBlock", "Bottleneck", "ResNet", "SEModule", "seresnet18", "seresnet34", "seresnet50", "seresnet101",
+    "seresnet152", "seresnext50_32x4d", "seresnext101_32x8d", "resnet18", "resnet34", "resnet50",
     "resnet101", "resnet152", "resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d", "wide_resnet50_2",
     "wide_resnet101_2", "CifarBlock", "CifarResNet18", "build_model",
 ]
@@ -39,19 +40,37 @@ def conv1x1(cin: int, cout: int, stride: int = 1) -> nn.Conv2d:
     return nn.Conv2d(cin, cout, kernel_size=1, stride=stride, bias=False)
 
 
+class SEModule(nn.Module):
+    """Squeeze-and-excitation gate (Hu et al. 2018) in timm's ``SEModule`` layout: ``fc1`` / ``fc2`` are 1x1 convs
+    with a bias, the squeezed width is ``max(8, channels // reduction)``; returns ``x * sigmoid(fc2(relu(fc1(mean))))``."""
+
+    def __init__(self, channels: int, reduction: int = 16):
+        super().__init__()
+        rd = max(8, channels // reduction)
+        self.fc1 = nn.Conv2d(channels, rd, kernel_size=1, bias=True)
+        self.fc2 = nn.Conv2d(rd, channels, kernel_size=1, bias=True)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        s = torch.sigmoid(self.fc2(F.relu(self.fc1(x.mean((2, 3), keepdim=True)))))
+        return x * s
+
+
 class BasicBlock(nn.Module):
-    """torchvision BasicBlock (two 3x3 convs), keys conv1/bn1/conv2/bn2/downsample.{0,1}."""
+    """torchvision BasicBlock (two 3x3 convs), keys conv1/bn1/conv2/bn2/downsample.{0,1}. ``se_reduction`` > 0: an
+    :class:`SEModule` ``se`` gates the output of bn2 before the shortcut add (timm's seresnet18 / 34)."""
 
     expansion = 1
 
     def __init__(self, inplanes: int, planes: int, stride: int = 1,
-                 downsample: Optional[nn.Module] = None):
+                 downsample: Optional[nn.Module] = None, se_reduction: int = 0):
         super().__init__()
         self.conv1 = conv3x3(inplanes, planes, stride)
         self.bn1 = nn.BatchNorm2d(planes)
         self.relu = nn.ReLU(inplace=True)
         self.conv2 = conv3x3(planes, planes)
         self.bn2 = nn.BatchNorm2d(planes)
+        if se_reduction > 0:  # (no attribute at all without it: the module tree and the RNG stream of before)
+            self.se = SEModule(planes, se_reduction)
         self.downsample = downsample
         self.stride = stride
 
@@ -59,6 +78,9 @@ class BasicBlock(nn.Module):
         identity = x
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
+        se = getattr(self, "se", None)
+        if se is not None:
+            out = se(out)
         if self.downsample is not None:
             identity = self.downsample(x)
         return self.relu(out + identity)
@@ -66,12 +88,14 @@ class BasicBlock(nn.Module):
 
 class Bottleneck(nn.Module):
     """torchvision v1.5 Bottleneck: stride lives on the 3x3 conv (SURVEY.md §2.4 note). ``groups`` / ``base_width``
-    (ResNeXt, Wide ResNet): the inner width is ``int(planes * base_width / 64) * groups`` and the 3x3 conv is grouped."""
+    (ResNeXt, Wide ResNet): the inner width is ``int(planes * base_width / 64) * groups`` and the 3x3 conv is grouped.
+    ``se_reduction`` > 0: an :class:`SEModule` ``se`` gates the output of bn3 before the shortcut add (SE-ResNet)."""
 
     expansion = 4
 
     def __init__(self, inplanes: int, planes: int, stride: int = 1,
-                 downsample: Optional[nn.Module] = None, groups: int = 1, base_width: int = 64):
+                 downsample: Optional[nn.Module] = None, groups: int = 1, base_width: int = 64,
+                 se_reduction: int = 0):
         super().__init__()
         width = int(planes * base_width / 64) * groups
         self.conv1 = conv1x1(inplanes, width)
@@ -80,6 +104,8 @@ class Bottleneck(nn.Module):
         self.bn2 = nn.BatchNorm2d(width)
         self.conv3 = conv1x1(width, planes * self.expansion)
         self.bn3 = nn.BatchNorm2d(planes * self.expansion)
+        if se_reduction > 0:
+            self.se = SEModule(planes * self.expansion, se_reduction)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
         self.stride = stride
@@ -89,6 +115,9 @@ class Bottleneck(nn.Module):
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
         out = self.bn3(self.conv3(out))
+        se = getattr(self, "se", None)
+        if se is not None:
+            out = se(out)
         if self.downsample is not None:
             identity = self.downsample(x)
         return self.relu(out + identity)
@@ -100,12 +129,17 @@ class ResNet(nn.Module):
     ``in_channels`` != 3 reproduces the Ray FashionMNIST variant that swaps conv1 for
     ``Conv2d(1, 64, 7, 2, 3)`` (`/root/reference/05_ray/01_fashion_mnist_pytorch_ray.ipynb:169-174`).
     ``groups`` / ``width_per_group`` (Bottleneck only): ResNeXt (32 x 4d, 32 x 8d, 64 x 4d) and Wide ResNet (1 x 128).
+    ``se_reduction`` > 0: every block gets a squeeze-and-excitation gate of that reduction (SE-ResNet / SE-ResNeXt).
     """
 
     def __init__(self, block: Type[Union[BasicBlock, Bottleneck]], layers: Sequence[int],
                  num_classes: int = 1000, in_channels: int = 3,
-                 zero_init_residual: bool = False, groups: int = 1, width_per_group: int = 64):
+                 zero_init_residual: bool = False, groups: int = 1, width_per_group: int = 64,
+                 se_reduction: int = 0):
         super().__init__()
+        if se_reduction < 0:
+            raise ValueError(f"se_reduction must be >= 0, got {se_reduction}")
+        self.se_reduction = int(se_reduction)
         if (groups != 1 or width_per_group != 64) and block is not Bottleneck:
             raise ValueError("groups / width_per_group need the Bottleneck block")
         self.groups, self.base_width = groups, width_per_group
@@ -133,6 +167,8 @@ class ResNet(nn.Module):
                 nn.BatchNorm2d(planes * block.expansion),
             )
         kw = dict(groups=self.groups, base_width=self.base_width) if block is Bottleneck else {}
+        if self.se_reduction:
+            kw["se_reduction"] = self.se_reduction
         layers: List[nn.Module] = [block(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
@@ -204,6 +240,16 @@ def wide_resnet101_2(num_classes: int = 1000, **kw) -> ResNet:
     return ResNet(Bottleneck, [3, 4, 23, 3], num_classes=num_classes, width_per_group=128, **kw)
 
 
+def _se(factory):
+    return lambda num_classes=1000, **kw: factory(num_classes=num_classes, se_reduction=16, **kw)
+
+
+# timm's seresnet* / seresnext*: every block gated, reduction 16
+seresnet18, seresnet34, seresnet50 = _se(resnet18), _se(resnet34), _se(resnet50)
+seresnet101, seresnet152 = _se(resnet101), _se(resnet152)
+seresnext50_32x4d, seresnext101_32x8d = _se(resnext50_32x4d), _se(resnext101_32x8d)
+
+
 # --------------------------------------------------------------------------------------
 # CIFAR-stem ResNet-18 of /root/reference/setup/resnet18.py (keys: conv1, bn1,
 # layer{1-4}.{0,1}.{conv1,bn1,conv2,bn2,skip_connection.{0,1}}, fc — SURVEY.md §5.4).
@@ -260,6 +306,8 @@ _FACTORIES: dict = {
     "resnet101": resnet101, "resnet152": resnet152,
     "resnext50_32x4d": resnext50_32x4d, "resnext101_32x8d": resnext101_32x8d, "resnext101_64x4d": resnext101_64x4d,
     "wide_resnet50_2": wide_resnet50_2, "wide_resnet101_2": wide_resnet101_2,
+    "seresnet18": seresnet18, "seresnet34": seresnet34, "seresnet50": seresnet50, "seresnet101": seresnet101,
+    "seresnet152": seresnet152, "seresnext50_32x4d": seresnext50_32x4d, "seresnext101_32x8d": seresnext101_32x8d,
     "cifar_resnet18": lambda num_classes=10, **kw: CifarResNet18(num_classes, **kw),
 }
 

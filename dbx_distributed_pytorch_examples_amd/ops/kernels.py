@@ -1312,7 +1312,7 @@ def avgpool_fwd(x, out):
     N, H, W, Cc = x.shape
     _chk(x, torch.bfloat16, "x")
     _chk(out, torch.bfloat16, "out", N * Cc)
-    C().avgpool_fwd(x.data_ptr(), out.data_ptr(), N, H * W, Cc, stream_ptr())
+    C().avgpool_fwd(x.data_ptr(), out.data_ptr(), N, H * W, Cc, stream_ptr(), 0, 0)
 
 
 @_dispatch
@@ -1321,6 +1321,177 @@ def avgpool_bwd(dout, dx):
     _chk(dout, torch.bfloat16, "dout", N * Cc)
     _chk(dx, torch.bfloat16, "dx")
     C().avgpool_bwd(dout.data_ptr(), dx.data_ptr(), N, H * W, Cc, stream_ptr())
+
+
+# ---- squeeze-and-excitation (csrc/se_ops.hip) ---------------------------------------------------------------------
+SE_RD_MIN, SE_RD_MAX = 8, 256  # squeezed channels the excite kernels hold (kSeRdMax)
+# dbx::SeArgs (csrc/abi.h), in order: 32 pointers, then 8 int32
+_SE_PTRS = ("y", "g", "res", "out", "gout", "mbits", "scale", "shift", "mean", "invstd", "gamma", "beta", "rsc",
+            "rsh", "coeff", "zsum", "gate", "A", "B", "dz", "zq", "h", "dpre1", "part", "wa", "ba", "wb", "bb", "bstats")
+_SE_INTS = ("N", "HW", "C", "rd", "nsplit", "nshard", "res_mode")
+SE_SQUEEZE, SE_EXCITE, SE_TAIL, SE_BWD_REDUCE, SE_EXCITE_BWD, SE_BWD_APPLY = 1, 2, 3, 4, 5, 6
+
+
+def se_nsplit(HW: int) -> int:
+    """Row ranges the SE reductions cut a sample's map into: one up to 256 pixels, at most 16."""
+    return min(16, (HW + 255) // 256)
+
+
+def se_rd_supported(C: int, rd: int) -> bool:
+    """Channel counts the SE kernels take: ``C % 64 == 0`` and ``rd`` a multiple of 8 in 8..256."""
+    return C > 0 and C % 64 == 0 and SE_RD_MIN <= rd <= SE_RD_MAX and rd % 8 == 0
+
+
+def _se_launch(op: int, **f) -> None:
+    """Pack a host ``dbx::SeArgs`` from tensors / ints by field name and run ``dbx_se_op`` (reached through
+    avgpool_fwd's binding: a nonzero ``se_op``)."""
+    import numpy as np
+    buf = np.zeros(32 * 8 + 8 * 4, dtype=np.uint8)
+    buf[:8 * len(_SE_PTRS)].view(np.uint64)[:] = [_p(f.get(k)) for k in _SE_PTRS]
+    buf[256:256 + 4 * len(_SE_INTS)].view(np.int32)[:] = [int(f.get(k, 0)) for k in _SE_INTS]
+    C().avgpool_fwd(0, 0, 0, 0, 0, stream_ptr(), op, buf.ctypes.data)
+
+
+def _se_shape(y, what: str) -> Tuple[int, int, int]:
+    """(N, HW, C) of an NHWC bf16 tensor the SE kernels take."""
+    _chk(y, torch.bfloat16, what)
+    if y.dim() != 4:
+        raise ValueError(f"{what}: expected [N, H, W, C], got shape {tuple(y.shape)}")
+    N, H, W, Cc = y.shape
+    if Cc % 64 or N < 1 or H * W < 1:
+        raise ValueError(f"{what}: the SE kernels need C % 64 == 0 and a non-empty map, got shape {tuple(y.shape)}")
+    return N, H * W, Cc
+
+
+def _se_tab(t, name: str, n: int, dtype=torch.float32):
+    _chk(t, dtype, name, n)
+    return t
+
+
+def _se_part(ws, N: int, HW: int, Cc: int, dev):
+    """The fp32 partial sums of a split reduction [nsplit, 2, N, C]: ``ws`` (checked) or a fresh buffer."""
+    ns = se_nsplit(HW)
+    if ns == 1:
+        return ns, None
+    if ws is None:
+        ws = torch.empty(ns * 2 * N * Cc, device=dev, dtype=torch.float32)
+    _chk(ws, torch.float32, "ws")
+    if ws.numel() < ns * 2 * N * Cc:
+        raise ValueError(f"ws: {ws.numel()} elements, the split reduction needs {ns * 2 * N * Cc}")
+    return ns, ws
+
+
+@_dispatch
+def se_squeeze(y, zsum, ws=None):
+    """zsum[n, c] = sum over the map of y[n, :, :, c] (fp32, one summation order: two runs agree bit for bit).
+    ``ws``: fp32 scratch of ``se_nsplit(HW) * 2 * N * C`` elements for maps of more than 256 pixels (allocated
+    when absent)."""
+    N, HW, Cc = _se_shape(y, "y")
+    _se_tab(zsum, "zsum", N * Cc)
+    ns, part = _se_part(ws, N, HW, Cc, y.device)
+    _se_launch(SE_SQUEEZE, y=y, zsum=zsum, part=part, N=N, HW=HW, C=Cc, nsplit=ns)
+    return zsum
+
+
+def _se_excite_shapes(zsum, w_rd_c, w_c_rd, rd_tabs, c_tabs):
+    N, Cc = zsum.shape
+    rd = w_rd_c.numel() // Cc
+    if not se_rd_supported(Cc, rd):
+        raise ValueError(f"the SE excite kernels need C % 64 == 0 and rd % 8 == 0 in {SE_RD_MIN}..{SE_RD_MAX}, "
+                         f"got C={Cc}, rd={rd}")
+    _chk(w_rd_c, torch.bfloat16, "the [rd, C] weight", rd * Cc)
+    _chk(w_c_rd, torch.bfloat16, "the [C, rd] weight", rd * Cc)
+    for name, (t, dt) in rd_tabs.items():
+        _se_tab(t, name, N * rd, dt)
+    for name, (t, dt) in c_tabs.items():
+        _se_tab(t, name, N * Cc, dt)
+    return N, Cc, rd
+
+
+@_dispatch
+def se_excite(zsum, scale, shift, hw, w1_16, b1, w2_16, b2, zq, h, gate):
+    """The SE gate of every sample in one launch (MFMA): ``zq = bf16(scale * zsum / hw + shift)`` [N, C],
+    ``h = bf16(relu(zq W1^T + b1))`` [N, rd], ``gate = sigmoid(h W2^T + b2)`` [N, C] fp32. ``w1_16`` [rd, C] and
+    ``w2_16`` [C, rd] bf16, the biases fp32."""
+    N, Cc, rd = _se_excite_shapes(zsum, w1_16, w2_16, {"h": (h, torch.bfloat16)},
+                                  {"zsum": (zsum, torch.float32), "zq": (zq, torch.bfloat16),
+                                   "gate": (gate, torch.float32)})
+    for t, nm, n in ((scale, "scale", Cc), (shift, "shift", Cc), (b1, "b1", rd), (b2, "b2", Cc)):
+        _se_tab(t, nm, n)
+    if int(hw) < 1:
+        raise ValueError(f"hw must be at least 1, got {hw}")
+    _se_launch(SE_EXCITE, zsum=zsum, scale=scale, shift=shift, wa=w1_16, ba=b1, wb=w2_16, bb=b2, zq=zq, h=h,
+               gate=gate, N=N, HW=int(hw), C=Cc, rd=rd)
+    return gate
+
+
+@_dispatch
+def se_tail(y, scale, shift, gate, out, *, res=None, res_scale=None, res_shift=None, mbits=None):
+    """out = relu(gate[n, c] * (scale_c * y + shift_c) + r), r = ``res`` or ``res * res_scale + res_shift``; one fp32
+    evaluation, one rounding. ``mbits``: the 1-bit ReLU mask of ``out`` in :func:`bn_apply`'s format."""
+    N, HW, Cc = _se_shape(y, "y")
+    _chk(out, torch.bfloat16, "out", y.numel())
+    _se_tab(gate, "gate", N * Cc)
+    _se_tab(scale, "scale", Cc), _se_tab(shift, "shift", Cc)
+    mode = 0
+    if res is not None:
+        _chk(res, torch.bfloat16, "res", y.numel())
+        mode = 1
+        if res_scale is not None:
+            _se_tab(res_scale, "res_scale", Cc), _se_tab(res_shift, "res_shift", Cc)
+            mode = 2
+    if mbits is not None:
+        _chk(mbits, torch.uint8, "mbits", y.numel() // 8)
+    _se_launch(SE_TAIL, y=y, scale=scale, shift=shift, gate=gate, out=out, res=res, rsc=res_scale, rsh=res_shift,
+               mbits=mbits, N=N, HW=HW, C=Cc, res_mode=mode)
+    return out
+
+
+@_dispatch
+def se_bwd_reduce(g, mbits, y, mean, invstd, A, B, ws=None):
+    """With gm = g where the mask bit is set, else 0: ``A[n, c] = sum_hw gm``, ``B[n, c] = sum_hw gm * xhat``
+    (xhat = (y - mean) * invstd), fp32 in :func:`se_squeeze`'s fixed order and work split (``ws`` as there)."""
+    N, HW, Cc = _se_shape(y, "y")
+    _chk(g, torch.bfloat16, "g", y.numel())
+    _chk(mbits, torch.uint8, "mbits", y.numel() // 8)
+    for t, nm, n in ((mean, "mean", Cc), (invstd, "invstd", Cc), (A, "A", N * Cc), (B, "B", N * Cc)):
+        _se_tab(t, nm, n)
+    ns, part = _se_part(ws, N, HW, Cc, y.device)
+    _se_launch(SE_BWD_REDUCE, y=y, g=g, mbits=mbits, mean=mean, invstd=invstd, A=A, B=B, part=part, N=N, HW=HW, C=Cc,
+               nsplit=ns)
+
+
+@_dispatch
+def se_excite_bwd(A, B, gate, h, zsum, hw, gamma, beta, mean, invstd, w2_16, w1_16, dpre2, dpre1, dz, bstats):
+    """Backward of :func:`se_excite` and the gated BN's backward moments, from the per-sample tables alone:
+    ``dpre2 = bf16((gamma B + beta A) gate (1 - gate))`` [N, C], ``dpre1 = bf16((dpre2 W2) (h > 0))`` [N, rd],
+    ``dz = dpre1 W1`` [N, C] fp32 (the gradient of the squeezed mean); then with du = gm gate + dz / hw
+    ``bstats`` = [sum du, sum du xhat] summed over n in fp64 in a fixed order, in the layout :func:`bn_bwd_coeff`
+    reads (shard 0; the others zeroed). ``w2_16`` [C, rd] and ``w1_16`` [rd, C]: the forward's bf16 weights."""
+    N, Cc, rd = _se_excite_shapes(A, w1_16, w2_16, {"h": (h, torch.bfloat16), "dpre1": (dpre1, torch.bfloat16)},
+                                  {"A": (A, torch.float32), "B": (B, torch.float32), "gate": (gate, torch.float32),
+                                   "zsum": (zsum, torch.float32), "dz": (dz, torch.float32),
+                                   "dpre2": (dpre2, torch.bfloat16)})
+    for t, nm in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (invstd, "invstd")):
+        _se_tab(t, nm, Cc)
+    nsh = _chk_stats(bstats, "bstats", Cc)
+    if int(hw) < 1:
+        raise ValueError(f"hw must be at least 1, got {hw}")
+    _se_launch(SE_EXCITE_BWD, A=A, B=B, gate=gate, h=h, zsum=zsum, gamma=gamma, beta=beta, mean=mean, invstd=invstd,
+               wa=w2_16, wb=w1_16, zq=dpre2, dpre1=dpre1, dz=dz, bstats=bstats, N=N, HW=int(hw), C=Cc, rd=rd,
+               nshard=nsh)
+
+
+@_dispatch
+def se_bwd_apply(g, mbits, y, gate, dz, coeff, dy, gout):
+    """``dy = k1 * (gm * gate + dz / HW) + k2 * y + k3`` with :func:`bn_bwd_coeff`'s ``coeff``; ``gout = gm``, the
+    masked block-output gradient (what the shortcut and a downsample BN consume)."""
+    N, HW, Cc = _se_shape(y, "y")
+    for t, nm in ((g, "g"), (dy, "dy"), (gout, "gout")):
+        _chk(t, torch.bfloat16, nm, y.numel())
+    _chk(mbits, torch.uint8, "mbits", y.numel() // 8)
+    _se_tab(gate, "gate", N * Cc), _se_tab(dz, "dz", N * Cc), _se_tab(coeff, "coeff", 3 * Cc)
+    _se_launch(SE_BWD_APPLY, g=g, mbits=mbits, y=y, gate=gate, dz=dz, coeff=coeff, out=dy, gout=gout, N=N, HW=HW, C=Cc)
 
 
 @_dispatch

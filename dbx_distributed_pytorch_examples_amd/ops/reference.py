@@ -333,6 +333,67 @@ def bn_bwd_apply(dout, y, coeff, dy, *, mask_mode, mref=None, scale=None, shift=
     dy.copy_((k[0] * g + k[1] * y.float() + k[2]).bfloat16())
 
 
+# ---- squeeze-and-excitation (csrc/se_ops.hip): the kernels' formulas and rounding points in torch -------------------
+def _mask_bits(mbits, shape):
+    w = 2 ** torch.arange(8, dtype=torch.int32)
+    return ((mbits.view(-1, 1).to(torch.int32) & w) != 0).reshape(shape)
+
+
+def se_squeeze(y, zsum, ws=None):
+    N, C = y.shape[0], y.shape[-1]
+    zsum.copy_(y.float().reshape(N, -1, C).sum(1))
+    return zsum
+
+
+def se_excite(zsum, scale, shift, hw, w1_16, b1, w2_16, b2, zq, h, gate):
+    zq.copy_((scale * (zsum / hw) + shift).bfloat16())
+    h.copy_(torch.relu(zq.float() @ w1_16.float().view(h.shape[1], -1).t() + b1).bfloat16())
+    gate.copy_(torch.sigmoid(h.float() @ w2_16.float().view(-1, h.shape[1]).t() + b2))
+    return gate
+
+
+def se_tail(y, scale, shift, gate, out, *, res=None, res_scale=None, res_shift=None, mbits=None):
+    N, C = y.shape[0], y.shape[-1]
+    f = gate.view(N, 1, 1, C) * (y.float() * scale + shift)
+    if res is not None:
+        r = res.float()
+        f = f + (r * res_scale + res_shift if res_scale is not None else r)
+    out.copy_(torch.relu(f).bfloat16())
+    if mbits is not None:
+        b = (out.reshape(-1, 8).float() > 0).to(torch.int32)
+        mbits.copy_((b * (2 ** torch.arange(8, dtype=torch.int32))).sum(1).to(torch.uint8))
+    return out
+
+
+def se_bwd_reduce(g, mbits, y, mean, invstd, A, B, ws=None):
+    N, C = y.shape[0], y.shape[-1]
+    gm = (g.float() * _mask_bits(mbits, g.shape)).reshape(N, -1, C)
+    A.copy_(gm.sum(1))
+    B.copy_((gm * ((y.float() - mean) * invstd).reshape(N, -1, C)).sum(1))
+
+
+def se_excite_bwd(A, B, gate, h, zsum, hw, gamma, beta, mean, invstd, w2_16, w1_16, dpre2, dpre1, dz, bstats):
+    C, rd = A.shape[1], h.shape[1]
+    dpre2.copy_(((gamma * B + beta * A) * gate * (1 - gate)).bfloat16())
+    dpre1.copy_(((dpre2.float() @ w2_16.float().view(C, rd)) * (h.float() > 0)).bfloat16())
+    dz.copy_(dpre1.float() @ w1_16.float().view(rd, C))
+    st = bstats.view(-1, 2, C)
+    st.zero_()
+    gt, dzd = gate.double(), dz.double()
+    st[0, 0] = (gt * A.double() + dzd).sum(0)
+    st[0, 1] = (gt * B.double() + dzd * ((zsum.double() - hw * mean.double()) * invstd.double() / hw)).sum(0)
+
+
+def se_bwd_apply(g, mbits, y, gate, dz, coeff, dy, gout):
+    N, C = y.shape[0], y.shape[-1]
+    hw = y.numel() // (N * C)
+    gm = g.float() * _mask_bits(mbits, g.shape)
+    k = coeff.view(3, C)
+    du = gm * gate.view(N, 1, 1, C) + dz.view(N, 1, 1, C) / hw
+    dy.copy_((k[0] * du + k[1] * y.float() + k[2]).bfloat16())
+    gout.copy_(gm.bfloat16())
+
+
 def bn_bwd_apply2(g, y1, coeff1, dy1, y2, coeff2, dy2, fin1=None, fin2=None):
     bn_bwd_apply(g, y1, coeff1, dy1, mask_mode=0, fin=fin1)
     bn_bwd_apply(g, y2, coeff2, dy2, mask_mode=0, fin=fin2)
