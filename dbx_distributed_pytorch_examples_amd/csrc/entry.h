@@ -61,14 +61,17 @@ int dbx_bn_bwd_apply(const bf16* dout, const bf16* mref, const bf16* y, const fl
                      const dbx::BnFin* fin);
 int dbx_bn_bwd_apply2(const bf16* g, const bf16* y1, const float* c1, bf16* dy1, const bf16* y2, const float* c2,
                       bf16* dy2, long long n, int C, hipStream_t st, const dbx::BnFin* fin1, const dbx::BnFin* fin2);
+// blur != 0 (all three): the anti-aliased down-sampling kernels of blur_ops.hip instead -- forwards to dbx_blur_op
+// below with the same tensors and sizes; arg, ymax, fin and the pool geometry K / stride / pad are then unread
 int dbx_maxpool_fwd(const bf16* x, const float* sc, const float* sh, bf16* out, unsigned char* arg, bf16* ymax, int N,
                     int H, int W, int C, int P, int Q, int K, int stride, int pad, int relu, hipStream_t st,
-                    const dbx::BnFin* fin);
+                    const dbx::BnFin* fin, int blur = 0);
 int dbx_maxpool_bwd(const bf16* dout, const unsigned char* arg, bf16* dx, int N, int H, int W, int C, int P, int Q,
-                    int K, int stride, int pad, hipStream_t st);
+                    int K, int stride, int pad, hipStream_t st, int blur = 0);
 int dbx_pool_bn_bwd(const bf16* dpool, const unsigned char* arg, const bf16* y, const float* sc, const float* sh,
                     const float* c1, const float* c2, const float* c3, bf16* dy, double* stats, int nshard, int N,
-                    int H, int W, int C, int P, int Q, int K, int stride, int pad, int apply, hipStream_t st);
+                    int H, int W, int C, int P, int Q, int K, int stride, int pad, int apply, hipStream_t st,
+                    int blur = 0);
 // se_op != 0: the squeeze-and-excitation kernels instead -- forwards to dbx_se_op(se_op, se_args) below; x, out and
 // the sizes are then unread
 int dbx_avgpool_fwd(const bf16* x, bf16* out, int N, int HW, int C, hipStream_t st, int se_op,
@@ -145,6 +148,16 @@ int dbx_ta_stage_u8(const unsigned char* T_in, unsigned char* T_out, int* hist, 
 // op 1 se_squeeze, 2 se_excite, 3 se_tail, 4 se_bwd_reduce, 5 se_excite_bwd, 6 se_bwd_apply on the fields of *args (a
 // HOST struct, abi.h) that the op names. Python reaches it through avgpool_fwd's binding (a nonzero se_op there)
 int dbx_se_op(int op, const dbx::SeArgs* args, hipStream_t st);
+
+// ---- anti-aliased down-sampling, BlurPool (blur_ops.hip) ------------------------------------------------------------
+// reflect-pad 1, depthwise [1,2,1] x [1,2,1] / 16, stride 2: [N,H,W,C] <-> [N,P,Q,C], P = (H - 1) / 2 + 1, C % 64 == 0.
+// op 1 blur_fwd: out = blur(relu(a*sc + sh)) (sc / sh null: out = blur(a); relu: the ReLU of the prologue);
+// op 2 blur_bwd: out = blur^T(a); op 3 / 4 blur_bn_bwd reduce / apply: g = [y*sc + sh > 0] * blur^T(a), stats +=
+// [sum g, sum g * (y - c1) * c2] / out = c1*g + c2*y + c3. Python reaches it through the blur argument of the
+// max-pool bindings (maxpool_fwd: op 1, maxpool_bwd: op 2, pool_bn_bwd: op 3 + apply)
+int dbx_blur_op(int op, const bf16* a, const bf16* y, const float* sc, const float* sh, const float* c1,
+                const float* c2, const float* c3, bf16* out, double* stats, int nshard, int N, int H, int W, int C,
+                int P, int Q, int relu, hipStream_t st);
 
 // ---- classifier head (head_ops.hip) -----------------------------------------------------------------------------
 int dbx_small_gemm(int ta, int tb, int out_f32, int drop, const dbx::GemmArgs* args, hipStream_t st);

@@ -1054,7 +1054,9 @@ extern "C" int dbx_bn_bwd_apply2(const bf16* g, const bf16* y1, const float* c1,
 }
 extern "C" int dbx_maxpool_fwd(const bf16* x, const float* sc, const float* sh, bf16* out, unsigned char* arg,
                                bf16* ymax, int N, int H, int W, int C, int P, int Q, int K, int stride, int pad, int relu,
-                               hipStream_t st, const BnFin* fin) {
+                               hipStream_t st, const BnFin* fin, int blur) {
+  if (blur != 0)
+    return dbx_blur_op(1, x, nullptr, sc, sh, nullptr, nullptr, nullptr, out, nullptr, 0, N, H, W, C, P, Q, relu, st);
   if (C % 8) return -1;
   if (C / 8 > 256) return -1;
   if (fin && !sc) return -2;
@@ -1068,7 +1070,10 @@ extern "C" int dbx_maxpool_fwd(const bf16* x, const float* sc, const float* sh, 
   RET_LAST;
 }
 extern "C" int dbx_maxpool_bwd(const bf16* dout, const unsigned char* arg, bf16* dx, int N, int H, int W, int C, int P,
-                               int Q, int K, int stride, int pad, hipStream_t st) {
+                               int Q, int K, int stride, int pad, hipStream_t st, int blur) {
+  if (blur != 0)
+    return dbx_blur_op(2, dout, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, dx, nullptr, 0, N, H, W, C, P,
+                       Q, 0, st);
   if (C % 8) return -1;
   const long long total = (long long)N * H * W * (C / 8);
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total)), dim3(256), 0, st, dout, arg, dx, N, H, W, C, P, Q, K,
@@ -1078,7 +1083,9 @@ extern "C" int dbx_maxpool_bwd(const bf16* dout, const unsigned char* arg, bf16*
 extern "C" int dbx_pool_bn_bwd(const bf16* dpool, const unsigned char* arg, const bf16* y, const float* sc,
                                const float* sh, const float* c1, const float* c2, const float* c3, bf16* dy,
                                double* stats, int nshard, int N, int H, int W, int C, int P, int Q, int K, int stride,
-                               int pad, int apply, hipStream_t st) {
+                               int pad, int apply, hipStream_t st, int blur) {
+  if (blur != 0)
+    return dbx_blur_op(apply ? 4 : 3, dpool, y, sc, sh, c1, c2, c3, dy, stats, nshard, N, H, W, C, P, Q, 1, st);
   if (C % 8 || 256 % (C / 8) || (K + stride - 1) / stride > 2) return -1;
   if ((long long)N * H * W * C >= (1LL << 31) || (long long)N * P * Q * C >= (1LL << 31)) return -2;
   const dim3 g(grid_for((long long)N * H, 1, apply ? 8192 : 2048)), b(256);

@@ -20,7 +20,8 @@ optimizer already holding them, stay valid; conv weights as channels_last views)
 ``model.state_dict()`` / ``load_state_dict`` / checkpoint files keep torchvision layouts.
 
 Supported module trees: ``models.ResNet`` (BasicBlock / Bottleneck, any in_channels <= 4, every block with or without
-a squeeze-and-excitation gate ``se``; Bottleneck also widened
+a squeeze-and-excitation gate ``se``, and with or without anti-aliased down-sampling (``blur_pool``: a ``BlurPool2d``
+behind the stride-2 blocks' 3x3 conv and behind a stride-1 stem pool; csrc/blur_ops.hip); Bottleneck also widened
 (Wide ResNet) or with a grouped 3x3 conv2 (ResNeXt: ``K.group_conv_supported``, 4 to 64 channels per group)) and
 ``models.CifarResNet18``; everything else trains through the autograd path (engine.autograd_step).
 """
@@ -36,7 +37,7 @@ import torch
 import torch.nn as nn
 
 from ..engine_config import EngineConfig
-from ..models.resnet import BasicBlock, Bottleneck, CifarBlock, CifarResNet18, ResNet, SEModule
+from ..models.resnet import BasicBlock, BlurPool2d, Bottleneck, CifarBlock, CifarResNet18, ResNet, SEModule
 from ..ops import kernels as K
 from .schedule import ScheduleContext, StepSchedule, resolve_schedule
 
@@ -181,6 +182,10 @@ class BlockL:
     dsbuf: Optional[torch.Tensor] = None
     dx: Optional[torch.Tensor] = None                       # grad wrt block input
     se: Optional[SEL] = None                                # the gate on the last BN's output (SE-ResNet)
+    # anti-aliased down-sampling: the index j of the conv whose BN + ReLU output a BlurPool2d halves (acts[j] is the
+    # blurred tensor, the plain operand of conv j + 1), None without one; blur_hw = ((H, W) before, (P, Q) behind)
+    blur: Optional[int] = None
+    blur_hw: Optional[Tuple[Tuple[int, int], Tuple[int, int]]] = None
 
 
 class ResNetProgram:
@@ -328,16 +333,41 @@ class ResNetProgram:
                             f"{K.SE_RD_MIN}..{K.SE_RD_MAX}, got C={C}, rd={rd}")
         return SEL(name, mod, C, rd)
 
+    @staticmethod
+    def _blur(name: str, mod, C: int, H: int, W: int, conv: Optional[ConvL] = None):
+        """A BlurPool2d of ``C`` channels on an H x W map (behind ``conv``, run at stride 1): ((H, W), (P, Q))."""
+        if not (isinstance(mod, BlurPool2d) and mod.stride == 2 and mod.channels == C
+                and tuple(mod.filt.shape) == (C, 1, 3, 3)):
+            raise TypeError(f"{name}: unsupported down-sampling (a models.BlurPool2d of {C} channels, filter size 3, "
+                            f"stride 2 is expected)")
+        if conv is not None and (conv.R, conv.S, conv.stride, conv.pad) != (3, 3, 1, 1):
+            raise TypeError(f"{name}: a BlurPool2d follows a 3x3 stride-1 conv, {conv.name} is not one")
+        if not K.blur_supported(C, H, W):
+            raise TypeError(f"{name}: the blur kernels take C % 64 == 0 and a map of at least 2 x 2, got C={C}, "
+                            f"{H} x {W}")
+        return (H, W), K.blur_out_hw(H, W)
+
     def _build_layers(self):
         m = self.model
         self.stem = self._conv("conv1", m.conv1, self.H, self.W, stem=True)
         self.stem_bn = BNL("bn1", m.bn1, m.bn1.num_features)
         mp = m.maxpool
+        # the anti-aliased stem: Sequential(MaxPool2d(3, 1, 1), BlurPool2d) -- the pool at full resolution, then the blur
+        self.stem_blur = isinstance(mp, nn.Sequential)
+        if self.stem_blur:
+            if not (len(mp) == 2 and isinstance(mp[0], nn.MaxPool2d) and isinstance(mp[1], BlurPool2d)):
+                raise TypeError("maxpool: unsupported stem pool (a MaxPool2d, or Sequential(MaxPool2d, BlurPool2d))")
+            self._blur("maxpool.1", mp[1], self.stem.OC, self.stem.OH, self.stem.OW)
+            mp = mp[0]
+        if not isinstance(mp, nn.MaxPool2d):
+            raise TypeError(f"maxpool: unsupported stem pool {type(mp).__name__}")
         self.pool_k, self.pool_s, self.pool_p = mp.kernel_size, mp.stride, mp.padding
         ph = (self.stem.OH + 2 * self.pool_p - self.pool_k) // self.pool_s + 1
         pw = (self.stem.OW + 2 * self.pool_p - self.pool_k) // self.pool_s + 1
         self.pool_hw = (ph, pw)
-        h, w, c = ph, pw, self.stem.OC
+        if self.stem_blur and (ph, pw) != (self.stem.OH, self.stem.OW):
+            raise TypeError("maxpool: the pool in front of a BlurPool2d keeps the resolution (MaxPool2d(3, 1, 1))")
+        h, w, c = (*(K.blur_out_hw(ph, pw) if self.stem_blur else (ph, pw)), self.stem.OC)
         self.blocks: List[BlockL] = []
         for li in range(1, 5):
             layer = getattr(m, f"layer{li}")
@@ -346,7 +376,8 @@ class ResNetProgram:
                 if isinstance(blk, Bottleneck):
                     c1 = self._conv(f"{pre}.conv1", blk.conv1, h, w)
                     c2 = self._conv(f"{pre}.conv2", blk.conv2, c1.OH, c1.OW)
-                    c3 = self._conv(f"{pre}.conv3", blk.conv3, c2.OH, c2.OW)
+                    bhw = self._blur(f"{pre}.blur", blk.blur, c2.OC, c2.OH, c2.OW, c2) if hasattr(blk, "blur") else None
+                    c3 = self._conv(f"{pre}.conv3", blk.conv3, *(bhw[1] if bhw else (c2.OH, c2.OW)))
                     if c1.groups != 1 or c3.groups != 1:
                         raise TypeError(f"{pre}: only a bottleneck's conv2 may be grouped")
                     convs = [c1, c2, c3]
@@ -357,7 +388,8 @@ class ResNetProgram:
                     ds = blk.downsample
                 elif isinstance(blk, (BasicBlock, CifarBlock)):
                     c1 = self._conv(f"{pre}.conv1", blk.conv1, h, w)
-                    c2 = self._conv(f"{pre}.conv2", blk.conv2, c1.OH, c1.OW)
+                    bhw = self._blur(f"{pre}.blur", blk.blur, c1.OC, c1.OH, c1.OW, c1) if hasattr(blk, "blur") else None
+                    c2 = self._conv(f"{pre}.conv2", blk.conv2, *(bhw[1] if bhw else (c1.OH, c1.OW)))
                     if c1.groups != 1 or c2.groups != 1:
                         raise TypeError(f"{pre}: only a bottleneck's conv2 may be grouped")
                     convs = [c1, c2]
@@ -378,6 +410,10 @@ class ResNetProgram:
                     dsb = BNL(f"{pre}.{dsn}.1", ds[1], ds[1].num_features)
                 last = convs[-1]
                 blk_l = BlockL(kind, convs, bns, dsc, dsb, (h, w, c), (last.OH, last.OW, last.OC))
+                if bhw is not None:
+                    blk_l.blur, blk_l.blur_hw = len(convs) - 2, bhw
+                    if dsc is not None and (dsc.OH, dsc.OW) != (last.OH, last.OW):
+                        raise TypeError(f"{pre}: the shortcut and the blurred branch give different sizes")
                 if getattr(blk, "se", None) is not None:
                     blk_l.se = self._se(f"{pre}.se", blk.se, last.OC)
                 self.blocks.append(blk_l)
@@ -561,7 +597,9 @@ class ResNetProgram:
         self.x4 = torch.zeros(N, self.H, self.W, 4, device=dev, dtype=bf)
         self.y0 = E(N, st.OH, st.OW, st.OC)
         ph, pw = self.pool_hw
-        self.p0 = E(N, ph, pw, st.OC)
+        # (an anti-aliased stem: the pool's output at full resolution, blurred into p0; dp0 is its gradient)
+        self.pfull = E(N, ph, pw, st.OC) if self.stem_blur else None
+        self.p0 = E(N, *K.blur_out_hw(ph, pw), st.OC) if self.stem_blur else E(N, ph, pw, st.OC)
         self.parg = torch.empty(N, ph, pw, st.OC, device=dev, dtype=torch.uint8)
         self.dp0 = E(N, ph, pw, st.OC)
         # pooled-gradient buffer only for pool geometries the fused stem backward does not cover
@@ -574,15 +612,19 @@ class ResNetProgram:
         for b in self.blocks:
             b.ys = [E(N, cv.OH, cv.OW, cv.OC) for cv in b.convs]
             b.dys = [E(N, cv.OH, cv.OW, cv.OC) for cv in b.convs]
-            b.das = [E(N, cv.OH, cv.OW, cv.OC) for cv in b.convs[:-1]]
+            # (behind a blur the intermediate activation and its gradient have the blurred size)
+            ahw = [b.blur_hw[1] if j == b.blur else (cv.OH, cv.OW) for j, cv in enumerate(b.convs[:-1])]
+            b.das = [E(N, *ahw[j], cv.OC) for j, cv in enumerate(b.convs[:-1])]
             # BN outputs inside the block (inputs of convs 1..n-1), written in backward by the MASK_Y
             # dgrad epilogue that computes them for the ReLU mask anyway: the weight gradient then
             # reads them instead of re-applying BN+ReLU to every staged tile
             # (the input of a grouped conv, or of one wider than the BN prologue holds, is always materialised)
-            b.acts = [E(N, cv.OH, cv.OW, cv.OC) if self.act_writeback or self._plain_only(b.convs[j + 1]) else None
-                      for j, cv in enumerate(b.convs[:-1])]
+            # (and so is the blurred tensor, which only the forward can compute)
+            b.acts = [E(N, *ahw[j], cv.OC) if (self.act_writeback or self._plain_only(b.convs[j + 1]) or j == b.blur)
+                      else None for j, cv in enumerate(b.convs[:-1])]
             # acts[j] computed in the forward (eight-wave or grouped consumer conv j+1): see self.fast_mat
-            b.mat = [self._materialize(b.convs[j + 1]) and b.acts[j] is not None for j in range(len(b.convs) - 1)]
+            b.mat = [j == b.blur or (self._materialize(b.convs[j + 1]) and b.acts[j] is not None)
+                     for j in range(len(b.convs) - 1)]
             h, w, c = b.in_shape
             b.dx = E(N, h, w, c)
             if b.ds_conv is not None:
@@ -985,8 +1027,11 @@ class ResNetProgram:
         sfin = sbn.fin_f if (tr and self.fin_in and sbn.fin_f is not None) else None  # (finalized by the pool)
         if sfin is None:
             self._bn_fwd(sbn, N * st.OH * st.OW)
-        K.maxpool_fwd(self.y0, self.p0, self.parg, K=self.pool_k, stride=self.pool_s, pad=self.pool_p,
-                      scale=sbn.scale, shift=sbn.shift, relu=True, ymax=self.pymax if tr else None, fin=sfin)
+        K.maxpool_fwd(self.y0, self.pfull if self.stem_blur else self.p0, self.parg, K=self.pool_k, stride=self.pool_s,
+                      pad=self.pool_p, scale=sbn.scale, shift=sbn.shift, relu=True, ymax=self.pymax if tr else None,
+                      fin=sfin)
+        if self.stem_blur:
+            K.blur_fwd(self.pfull, self.p0)
         x = self.p0
         # ds_fwd_side: a downsample conv reads only the block input (written by the block's conv1
         # tail prologue): it runs on the side stream beside conv2 / conv3, launched like a deferred side
@@ -1006,6 +1051,12 @@ class ResNetProgram:
                                tail_res_shift=rsh, tail_out=pb.out, tail_bits=pb.obits if tr else None,
                                fin=self._ff(b.bns[0]), fin_in=pfin, fin_in_res=prfin)
                     pending = None
+                elif i > 0 and b.blur == i - 1:
+                    # BN + ReLU + blur in one pass (csrc/blur_ops.hip): the BN output at full resolution is never
+                    # written; the blurred tensor is this conv's plain operand (and its weight gradient's)
+                    K.blur_fwd(b.ys[i - 1], b.acts[i - 1], scale=prev_bn.scale, shift=prev_bn.shift, relu=True)
+                    K.conv_fwd(b.acts[i - 1], cv.w16, b.ys[i], R=cv.R, S=cv.S, stride=cv.stride, pad=cv.pad,
+                               stats=b.bns[i].stats if tr else None, fin=self._ff(b.bns[i]))
                 elif i > 0 and cv.groups > 1:  # materialised BN output -> grouped 3x3 (csrc/conv_group.hip)
                     K.bn_apply(b.ys[i - 1], prev_bn.scale, prev_bn.shift, b.acts[i - 1], relu=True)
                     K.group_conv_fwd(b.acts[i - 1], cv.w16, b.ys[i], groups=cv.groups, stride=cv.stride,
@@ -1376,6 +1427,7 @@ class ResNetProgram:
         pend, gin = None, None  # BN-backward apply deferred into the next dgrad's prologue
         ds_fold = None  # ... and the downsample BN's, into the downsample dgrad
         fuse3 = self._fuse3(b, last)  # conv3's BN-backward apply + dgrad + wgrad in one kernel
+        fold_lc = b.blur is None and self._fold(lc)  # (nothing is folded into the conv behind a blur)
         if b.se is not None:
             g = self._bwd_se_tail(b, self.dlast if last else self.blocks[i + 1].dx)
         elif last:
@@ -1414,7 +1466,7 @@ class ResNetProgram:
                 todo[id(dbn)] = (dbn, N * dc.OH * dc.OW)
             if last or b.se is not None:  # (an SE block: g is the masked scratch gradient, nothing is folded)
                 K.bn_bwd_apply(g, b.yd, dbn.coeff, b.dyd, mask_mode=K.MASK_NONE, fin=fin_of(dbn))
-            elif (fuse3 or self._fold(lc)) and self._fold(dc, dense=True):
+            elif (fuse3 or fold_lc) and self._fold(dc, dense=True):
                 # both tail BN applies folded into the dgrads of conv3 and of the downsample conv
                 ready(lbn)
                 ready(dbn)
@@ -1430,7 +1482,7 @@ class ResNetProgram:
                 f1, f2 = fin_of(lbn), fin_of(dbn)
                 K.bn_bwd_apply2(g, b.ys[-1], lbn.coeff, b.dys[-1], b.yd, dbn.coeff, b.dyd, fin1=f1, fin2=f2)
         elif not last and b.se is None:
-            if fuse3 or self._fold(lc):  # folded into conv3's dgrad prologue (it stores dys[-1] for the wgrad)
+            if fuse3 or fold_lc:  # folded into conv3's dgrad prologue (it stores dys[-1] for the wgrad)
                 ready(lbn)
                 pend = dict(bwd_y=b.ys[-1], bwd_coeff=lbn.coeff, dy_out=b.dys[-1])
                 gin = g
@@ -1448,6 +1500,16 @@ class ResNetProgram:
             act = b.acts[j - 1]
             kw, src = (pend, gin) if pend else ({}, b.dys[j])
             pend = None
+            if b.blur == j - 1:
+                # the conv behind a blur: its data gradient is the gradient of the blurred tensor (no mask epilogue);
+                # blur^T, the ReLU mask and the BN backward of the conv in front are one reduce / apply pair
+                assert not kw, "nothing is folded into the conv behind a blur"
+                K.conv_dgrad(src, cv.wt16, b.das[j - 1], R=cv.R, S=cv.S, stride=cv.stride, pad=cv.pad)
+                self._wgrad(b.dys[j], act, cv.grad, self.ws, R=cv.R, S=cv.S, stride=cv.stride, pad=cv.pad)
+                K.blur_bn_bwd_reduce(b.das[j - 1], b.ys[j - 1], pbn.scale, pbn.shift, pbn.mean, pbn.invstd, pbn.bstats)
+                self._coeff(pbn, N * pc.OH * pc.OW)
+                K.blur_bn_bwd_apply(b.das[j - 1], b.ys[j - 1], pbn.scale, pbn.shift, pbn.coeff, b.dys[j - 1])
+                continue
             if cv.groups > 1:
                 # grouped conv2: plain data gradient, then the ReLU mask and BN1's backward as standalone passes
                 # (not fused into the grouped kernel's epilogue); the weight gradient reads the forward's acts
@@ -1571,7 +1633,7 @@ class ResNetProgram:
     def _fuse3(self, b: BlockL, last: bool) -> bool:
         """Run block b's conv3 backward through K.conv_dwfused (the 64 -> 256 conv3 of the 56x56
         stage: its weight-gradient accumulators fit a workgroup's registers)."""
-        if not self.fuse_dw or last or b.kind != "bottleneck" or b.se is not None:
+        if not self.fuse_dw or last or b.kind != "bottleneck" or b.se is not None or b.blur is not None:
             return False
         c3 = b.convs[-1]
         return ((c3.R, c3.S, c3.stride, c3.pad) == (1, 1, 1, 0) and c3.OH >= self.cfg.fuse_dw_min_hw
@@ -1608,6 +1670,9 @@ class ResNetProgram:
                 return
             K.pool_bn_bwd_apply(dp, self.parg, self.y0, sbn.scale, sbn.shift, sbn.coeff, self.dy0, **pk)
         else:
+            if self.stem_blur:  # blur^T first: the gradient of the full-resolution pool output
+                K.blur_bwd(dp, self.dp0)
+                dp = self.dp0
             K.maxpool_bwd(dp, self.parg, self.da0, K=self.pool_k, stride=self.pool_s, pad=self.pool_p)
             self._bn_bwd(sbn, self.da0, self.y0, self.dy0, self.N * st.OH * st.OW, K.MASK_Y)
         # small steps (stem_wg_main, engine/schedule.py): with the batched side stream the stem weight gradient

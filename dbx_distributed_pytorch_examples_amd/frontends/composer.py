@@ -3,7 +3,8 @@
 ``Trainer(model, optimizers, train_dataloader, eval_dataloader, max_duration="2ep",
 algorithms=[LabelSmoothing(0.1), CutMix(1.0), ChannelsLast()], loggers=[MLFlowLogger(...)]).fit()``.
 Algorithms map onto the engine: label smoothing -> the CE target, CutMix / MixUp -> the batch-mixing step
-(soft-label CE; with both, each step takes one of the two), ChannelsLast -> a no-op marker (every GPU path here is NHWC end to end, K19).
+(soft-label CE; with both, each step takes one of the two), ChannelsLast -> a no-op marker (every GPU path here is NHWC end to end, K19),
+BlurPool -> the anti-aliased blocks and stem of ``models.ResNet(blur_pool=True)``, which the native program compiles.
 The model follows Composer's ``forward(batch)`` / ``loss(outputs, batch)`` convention
 (``models.ComposerResNet50``); plain modules work too.
 
@@ -52,6 +53,41 @@ class ChannelsLast(Algorithm):
     """NHWC memory format — the framework's native layout; kept for API parity."""
 
 
+class BlurPool(Algorithm):
+    """Composer's ``BlurPool(replace_convs, replace_maxpools, blur_first)`` for the ResNets of this package: anti-aliased
+    down-sampling (Zhang 2019), applied to the model in place with its parameters kept (``blur_pool=True`` of
+    ``models.ResNet``).
+
+    What is built is the Zhang / timm placement: a stride-2 block runs its 3x3 conv at stride 1 and a reflect-padded
+    ``[1,2,1] x [1,2,1] / 16`` blur at stride 2 follows that conv's BN + ReLU (``replace_convs``); the stem pool becomes
+    ``MaxPool2d(3, 1, 1)`` + the same blur (``replace_maxpools``; False keeps the stem pool). Composer's own
+    ``blur_first=True`` form -- a zero-padded blur in front of the strided conv -- is NOT what is built; the argument is
+    accepted for the signature only."""
+
+    def __init__(self, replace_convs: bool = True, replace_maxpools: bool = True, blur_first: bool = True):
+        if not replace_convs and not replace_maxpools:
+            raise ValueError("BlurPool: replace_convs and replace_maxpools are both False, nothing would change")
+        self.replace_convs, self.replace_maxpools, self.blur_first = replace_convs, replace_maxpools, blur_first
+
+    def apply(self, model: nn.Module) -> nn.Module:
+        from ..models.resnet import BasicBlock, Bottleneck, BlurPool2d, ResNet
+        net = model if isinstance(model, ResNet) else getattr(model, "model", None)
+        if not isinstance(net, ResNet):
+            raise TypeError(f"BlurPool rebuilds the ResNets of this package, got {type(model).__name__}")
+        if self.replace_convs:
+            for blk in net.modules():
+                if isinstance(blk, (BasicBlock, Bottleneck)) and blk.stride == 2 and not hasattr(blk, "blur"):
+                    conv = blk.conv1 if isinstance(blk, BasicBlock) else blk.conv2
+                    conv.stride = (1, 1)
+                    blk.blur = BlurPool2d(conv.out_channels, 2).to(conv.weight.device)
+        if self.replace_maxpools and isinstance(net.maxpool, nn.MaxPool2d):
+            net.maxpool = nn.Sequential(nn.MaxPool2d(kernel_size=3, stride=1, padding=1),
+                                        BlurPool2d(net.conv1.out_channels, 2).to(net.conv1.weight.device))
+        if self.replace_convs and self.replace_maxpools:
+            net.blur_pool = True
+        return model
+
+
 class ComposerModel(nn.Module):
     """Base class with Composer's hooks."""
 
@@ -87,6 +123,9 @@ class Trainer:
         from ..config import OptimizerConfig
         self.info = ddist.init_distributed(device=device if device in ("cpu", "cuda") else None)
         self.native = False
+        for a in algorithms:  # (model surgery first: the native program compiles the module tree it is given)
+            if isinstance(a, BlurPool):
+                a.apply(model)
         model = self._maybe_native(model, train_dataloader)
         smoothing = next((a.smoothing for a in algorithms if isinstance(a, LabelSmoothing)), 0.0)
         cut = next((a for a in algorithms if isinstance(a, CutMix)), None)

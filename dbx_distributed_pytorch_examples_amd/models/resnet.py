@@ -25,7 +25,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 __all__ = [
-    "BasicBlock", "Bottleneck", "ResNet", "SEModule", "seresnet18", "seresnet34", "seresnet50", "seresnet101",
+    "BasicBlock", "BlurPool2d", "Bottleneck", "ResNet", "SEModule", "resnetblur18", "resnetblur34", "resnetblur50",
+    "resnetblur101", "seresnet18", "seresnet34", "seresnet50", "seresnet101",
     "seresnet152", "seresnext50_32x4d", "seresnext101_32x8d", "resnet18", "resnet34", "resnet50",
     "resnet101", "resnet152", "resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d", "wide_resnet50_2",
     "wide_resnet101_2", "CifarBlock", "CifarResNet18", "build_model",
@@ -55,28 +56,54 @@ class SEModule(nn.Module):
         return x * s
 
 
+class BlurPool2d(nn.Module):
+    """Anti-aliased down-sampling (Zhang 2019, "Making Convolutional Networks Shift-Invariant Again"; timm's
+    ``BlurPool2d`` with filter size 3): reflect-pad by 1, then the depthwise filter ``[1,2,1] x [1,2,1] / 16`` at
+    ``stride``. Output size ``(H - 1) // stride + 1``. No parameters and no persistent buffer, so a model's state
+    dict does not know it is there."""
+
+    def __init__(self, channels: int, stride: int = 2):
+        super().__init__()
+        self.channels, self.stride = channels, stride
+        k = torch.tensor([1.0, 2.0, 1.0])
+        self.register_buffer("filt", (k[:, None] * k[None, :] / 16.0)[None, None].repeat(channels, 1, 1, 1),
+                             persistent=False)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return F.conv2d(F.pad(x, (1, 1, 1, 1), mode="reflect"), self.filt.to(x.dtype), stride=self.stride,
+                        groups=self.channels)
+
+
 class BasicBlock(nn.Module):
     """torchvision BasicBlock (two 3x3 convs), keys conv1/bn1/conv2/bn2/downsample.{0,1}. ``se_reduction`` > 0: an
-    :class:`SEModule` ``se`` gates the output of bn2 before the shortcut add (timm's seresnet18 / 34)."""
+    :class:`SEModule` ``se`` gates the output of bn2 before the shortcut add (timm's seresnet18 / 34).
+    ``blur_pool`` (timm's resnetblur18): a stride-2 block runs conv1 at stride 1 and a :class:`BlurPool2d` ``blur``
+    down-samples behind bn1 + ReLU; the shortcut is unchanged."""
 
     expansion = 1
 
     def __init__(self, inplanes: int, planes: int, stride: int = 1,
-                 downsample: Optional[nn.Module] = None, se_reduction: int = 0):
+                 downsample: Optional[nn.Module] = None, se_reduction: int = 0, blur_pool: bool = False):
         super().__init__()
-        self.conv1 = conv3x3(inplanes, planes, stride)
+        blur = blur_pool and stride == 2
+        self.conv1 = conv3x3(inplanes, planes, 1 if blur else stride)
         self.bn1 = nn.BatchNorm2d(planes)
         self.relu = nn.ReLU(inplace=True)
         self.conv2 = conv3x3(planes, planes)
         self.bn2 = nn.BatchNorm2d(planes)
         if se_reduction > 0:  # (no attribute at all without it: the module tree and the RNG stream of before)
             self.se = SEModule(planes, se_reduction)
+        if blur:  # (likewise)
+            self.blur = BlurPool2d(planes, stride)
         self.downsample = downsample
         self.stride = stride
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         identity = x
         out = self.relu(self.bn1(self.conv1(x)))
+        blur = getattr(self, "blur", None)
+        if blur is not None:
+            out = blur(out)
         out = self.bn2(self.conv2(out))
         se = getattr(self, "se", None)
         if se is not None:
@@ -89,23 +116,28 @@ class BasicBlock(nn.Module):
 class Bottleneck(nn.Module):
     """torchvision v1.5 Bottleneck: stride lives on the 3x3 conv (SURVEY.md §2.4 note). ``groups`` / ``base_width``
     (ResNeXt, Wide ResNet): the inner width is ``int(planes * base_width / 64) * groups`` and the 3x3 conv is grouped.
-    ``se_reduction`` > 0: an :class:`SEModule` ``se`` gates the output of bn3 before the shortcut add (SE-ResNet)."""
+    ``se_reduction`` > 0: an :class:`SEModule` ``se`` gates the output of bn3 before the shortcut add (SE-ResNet).
+    ``blur_pool`` (timm's resnetblur50): a stride-2 block runs conv2 at stride 1 and a :class:`BlurPool2d` ``blur``
+    down-samples behind bn2 + ReLU; the shortcut is unchanged."""
 
     expansion = 4
 
     def __init__(self, inplanes: int, planes: int, stride: int = 1,
                  downsample: Optional[nn.Module] = None, groups: int = 1, base_width: int = 64,
-                 se_reduction: int = 0):
+                 se_reduction: int = 0, blur_pool: bool = False):
         super().__init__()
         width = int(planes * base_width / 64) * groups
+        blur = blur_pool and stride == 2
         self.conv1 = conv1x1(inplanes, width)
         self.bn1 = nn.BatchNorm2d(width)
-        self.conv2 = conv3x3(width, width, stride, groups)
+        self.conv2 = conv3x3(width, width, 1 if blur else stride, groups)
         self.bn2 = nn.BatchNorm2d(width)
         self.conv3 = conv1x1(width, planes * self.expansion)
         self.bn3 = nn.BatchNorm2d(planes * self.expansion)
         if se_reduction > 0:
             self.se = SEModule(planes * self.expansion, se_reduction)
+        if blur:
+            self.blur = BlurPool2d(width, stride)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
         self.stride = stride
@@ -114,6 +146,9 @@ class Bottleneck(nn.Module):
         identity = x
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.relu(self.bn2(self.conv2(out)))
+        blur = getattr(self, "blur", None)
+        if blur is not None:
+            out = blur(out)
         out = self.bn3(self.conv3(out))
         se = getattr(self, "se", None)
         if se is not None:
@@ -130,13 +165,18 @@ class ResNet(nn.Module):
     ``Conv2d(1, 64, 7, 2, 3)`` (`/root/reference/05_ray/01_fashion_mnist_pytorch_ray.ipynb:169-174`).
     ``groups`` / ``width_per_group`` (Bottleneck only): ResNeXt (32 x 4d, 32 x 8d, 64 x 4d) and Wide ResNet (1 x 128).
     ``se_reduction`` > 0: every block gets a squeeze-and-excitation gate of that reduction (SE-ResNet / SE-ResNeXt).
+    ``blur_pool``: the anti-aliased ResNet (timm's resnetblurN) -- every stride-2 block down-samples with a
+    :class:`BlurPool2d` behind its 3x3 conv, run at stride 1, and the stem pool becomes
+    ``Sequential(MaxPool2d(3, 1, 1), BlurPool2d(64, 2))``. State-dict keys and parameter counts do not change.
     """
 
     def __init__(self, block: Type[Union[BasicBlock, Bottleneck]], layers: Sequence[int],
                  num_classes: int = 1000, in_channels: int = 3,
                  zero_init_residual: bool = False, groups: int = 1, width_per_group: int = 64,
-                 se_reduction: int = 0):
+                 se_reduction: int = 0, blur_pool: bool = False):
         super().__init__()
+        if blur_pool:  # (no attribute without it)
+            self.blur_pool = True
         if se_reduction < 0:
             raise ValueError(f"se_reduction must be >= 0, got {se_reduction}")
         self.se_reduction = int(se_reduction)
@@ -150,7 +190,8 @@ class ResNet(nn.Module):
         self.conv1 = nn.Conv2d(in_channels, 64, kernel_size=7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(64)
         self.relu = nn.ReLU(inplace=True)
-        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1)
+        self.maxpool = nn.MaxPool2d(kernel_size=3, stride=2, padding=1) if not blur_pool else nn.Sequential(
+            nn.MaxPool2d(kernel_size=3, stride=1, padding=1), BlurPool2d(64, stride=2))
         self.layer1 = self._make_layer(block, 64, layers[0])
         self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
         self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
@@ -169,6 +210,8 @@ class ResNet(nn.Module):
         kw = dict(groups=self.groups, base_width=self.base_width) if block is Bottleneck else {}
         if self.se_reduction:
             kw["se_reduction"] = self.se_reduction
+        if getattr(self, "blur_pool", False):
+            kw["blur_pool"] = True
         layers: List[nn.Module] = [block(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):
@@ -250,6 +293,15 @@ seresnet101, seresnet152 = _se(resnet101), _se(resnet152)
 seresnext50_32x4d, seresnext101_32x8d = _se(resnext50_32x4d), _se(resnext101_32x8d)
 
 
+def _blur(factory):
+    return lambda num_classes=1000, **kw: factory(num_classes=num_classes, blur_pool=True, **kw)
+
+
+# timm's resnetblur*: anti-aliased down-sampling in the stem and in every stride-2 block
+resnetblur18, resnetblur34, resnetblur50, resnetblur101 = (_blur(resnet18), _blur(resnet34), _blur(resnet50),
+                                                           _blur(resnet101))
+
+
 # --------------------------------------------------------------------------------------
 # CIFAR-stem ResNet-18 of /root/reference/setup/resnet18.py (keys: conv1, bn1,
 # layer{1-4}.{0,1}.{conv1,bn1,conv2,bn2,skip_connection.{0,1}}, fc — SURVEY.md §5.4).
@@ -308,6 +360,8 @@ _FACTORIES: dict = {
     "wide_resnet50_2": wide_resnet50_2, "wide_resnet101_2": wide_resnet101_2,
     "seresnet18": seresnet18, "seresnet34": seresnet34, "seresnet50": seresnet50, "seresnet101": seresnet101,
     "seresnet152": seresnet152, "seresnext50_32x4d": seresnext50_32x4d, "seresnext101_32x8d": seresnext101_32x8d,
+    "resnetblur18": resnetblur18, "resnetblur34": resnetblur34, "resnetblur50": resnetblur50,
+    "resnetblur101": resnetblur101,
     "cifar_resnet18": lambda num_classes=10, **kw: CifarResNet18(num_classes, **kw),
 }
 

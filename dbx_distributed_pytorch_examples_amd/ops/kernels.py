@@ -1222,7 +1222,7 @@ def maxpool_fwd(x, out, arg, *, K=3, stride=2, pad=1, scale=None, shift=None, re
         fin.run()
         fin = None
     C().maxpool_fwd(x.data_ptr(), _p(scale), _p(shift), out.data_ptr(), arg.data_ptr(), _p(ymax), N, H, W, Cc, P, Q,
-                    K, stride, pad, int(relu), stream_ptr(), fin.ptr() if fin else 0)
+                    K, stride, pad, int(relu), stream_ptr(), fin.ptr() if fin else 0, 0)
 
 
 @_dispatch
@@ -1232,7 +1232,7 @@ def maxpool_bwd(dout, arg, dx, *, K=3, stride=2, pad=1):
     _chk(dout, torch.bfloat16, "dout")
     _chk(arg, torch.uint8, "arg", dout.numel())
     _chk(dx, torch.bfloat16, "dx")
-    C().maxpool_bwd(dout.data_ptr(), arg.data_ptr(), dx.data_ptr(), N, H, W, Cc, P, Q, K, stride, pad, stream_ptr())
+    C().maxpool_bwd(dout.data_ptr(), arg.data_ptr(), dx.data_ptr(), N, H, W, Cc, P, Q, K, stride, pad, stream_ptr(), 0)
 
 
 def _pool_bn_bwd_check(dpool, arg, y, K, stride):
@@ -1260,7 +1260,7 @@ def pool_bn_bwd_reduce(dpool, arg, y, scale, shift, mean, invstd, stats, *, K=3,
     nsh = _chk_stats(stats, "stats", Cc)
     C().pool_bn_bwd(dpool.data_ptr(), arg.data_ptr(), y.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                     mean.data_ptr(), invstd.data_ptr(), 0, 0, stats.data_ptr(), nsh, N, H, W, Cc, Pp, Q, K,
-                    stride, pad, 0, stream_ptr())
+                    stride, pad, 0, stream_ptr(), 0)
 
 
 @_dispatch
@@ -1270,7 +1270,82 @@ def pool_bn_bwd_apply(dpool, arg, y, scale, shift, coeff, dy, *, K=3, stride=2, 
     _chk(dy, torch.bfloat16, "dy", y.numel())
     C().pool_bn_bwd(dpool.data_ptr(), arg.data_ptr(), y.data_ptr(), scale.data_ptr(), shift.data_ptr(),
                     coeff.data_ptr(), coeff.data_ptr() + 4 * Cc, coeff.data_ptr() + 8 * Cc, dy.data_ptr(), 0, 1,
-                    N, H, W, Cc, Pp, Q, K, stride, pad, 1, stream_ptr())
+                    N, H, W, Cc, Pp, Q, K, stride, pad, 1, stream_ptr(), 0)
+
+
+# ---- anti-aliased down-sampling, BlurPool (csrc/blur_ops.hip) --------------------------------------------------------
+# reflect-pad 1, depthwise [1,2,1] x [1,2,1] / 16, stride 2: [N, H, W, C] <-> [N, P, Q, C] with P, Q = blur_out_hw(H, W).
+# The kernels are reached through the blur argument of the max-pool bindings, whose arguments they mirror.
+blur_out_hw = _ref.blur_out_hw
+
+
+def blur_supported(C: int, H: int, W: int) -> bool:
+    return C >= 64 and C % 64 == 0 and H >= 2 and W >= 2
+
+
+def _chk_blur(full, small, fname: str, sname: str) -> Tuple[int, ...]:
+    """The full-resolution / blurred tensor pair of a blur launch: (N, H, W, C, P, Q)."""
+    if full.dim() != 4 or small.dim() != 4:
+        raise ValueError(f"blur: {fname} and {sname} are NHWC tensors")
+    N, H, W, Cc = full.shape
+    _ref.check_blur(Cc, H, W)
+    P, Q = blur_out_hw(H, W)
+    if tuple(small.shape) != (N, P, Q, Cc):
+        raise ValueError(f"blur: {sname} of a {tuple(full.shape)} {fname} is {(N, P, Q, Cc)}, got {tuple(small.shape)}")
+    _chk(full, torch.bfloat16, fname)
+    _chk(small, torch.bfloat16, sname)
+    if N > 65535:
+        raise ValueError(f"blur: at most 65535 images a launch, got {N}")
+    return N, H, W, Cc, P, Q
+
+
+@_dispatch
+def blur_fwd(y, out, *, scale=None, shift=None, relu=True):
+    """out = blur(relu(y*scale + shift)), fp32 with one rounding; without ``scale`` / ``shift``: out = blur(y)."""
+    dims = _chk_blur(y, out, "y", "out")
+    if (scale is None) != (shift is None):
+        raise ValueError("blur_fwd: scale and shift come together")
+    if scale is not None:
+        _chk(scale, torch.float32, "scale", dims[3])
+        _chk(shift, torch.float32, "shift", dims[3])
+    C().maxpool_fwd(y.data_ptr(), _p(scale), _p(shift), out.data_ptr(), 0, 0, *dims, 3, 2, 1, int(relu),
+                    stream_ptr(), 0, 1)
+    return out
+
+
+@_dispatch
+def blur_bwd(dout, dx):
+    """dx = blur^T(dout): the data gradient of a blur without a prologue (the stem's)."""
+    dims = _chk_blur(dx, dout, "dx", "dout")
+    C().maxpool_bwd(dout.data_ptr(), 0, dx.data_ptr(), *dims, 3, 2, 1, stream_ptr(), 1)
+
+
+def _chk_blur_bn(dpool, y, scale, shift, vecs) -> Tuple[int, ...]:
+    dims = _chk_blur(y, dpool, "y", "dpool")
+    for t, nm, n in ((scale, "scale", 1), (shift, "shift", 1)) + vecs:
+        _chk(t, torch.float32, nm, n * dims[3])
+    return dims
+
+
+@_dispatch
+def blur_bn_bwd_reduce(dpool, y, scale, shift, mean, invstd, stats):
+    """BN-backward reduce behind a blur: g = blur^T(dpool) masked by relu(y*scale + shift) > 0;
+    stats += [sum g, sum g*xhat]. g is never written."""
+    dims = _chk_blur_bn(dpool, y, scale, shift, ((mean, "mean", 1), (invstd, "invstd", 1)))
+    nsh = _chk_stats(stats, "stats", dims[3])
+    C().pool_bn_bwd(dpool.data_ptr(), 0, y.data_ptr(), scale.data_ptr(), shift.data_ptr(), mean.data_ptr(),
+                    invstd.data_ptr(), 0, 0, stats.data_ptr(), nsh, *dims, 3, 2, 1, 0, stream_ptr(), 1)
+
+
+@_dispatch
+def blur_bn_bwd_apply(dpool, y, scale, shift, coeff, dy):
+    """dy = k1*g + k2*y + k3 with g recomputed as in ``blur_bn_bwd_reduce``."""
+    dims = _chk_blur_bn(dpool, y, scale, shift, ((coeff, "coeff", 3),))
+    _chk(dy, torch.bfloat16, "dy", y.numel())
+    Cc = dims[3]
+    C().pool_bn_bwd(dpool.data_ptr(), 0, y.data_ptr(), scale.data_ptr(), shift.data_ptr(), coeff.data_ptr(),
+                    coeff.data_ptr() + 4 * Cc, coeff.data_ptr() + 8 * Cc, dy.data_ptr(), 0, 1, *dims, 3, 2, 1, 1,
+                    stream_ptr(), 1)
 
 
 def stem_bwd_supported(C: int, K: int, stride: int, R: int, S: int) -> bool:

@@ -473,6 +473,70 @@ def pool_bn_bwd_apply(dpool, arg, y, scale, shift, coeff, dy, *, K=3, stride=2, 
     dy.copy_((k[0] * g + k[1] * y.float() + k[2]).bfloat16())
 
 
+# ---- anti-aliased down-sampling (csrc/blur_ops.hip): reflect-pad 1, depthwise [1,2,1] x [1,2,1] / 16, stride 2 ------
+def blur_out_hw(h: int, w: int):
+    return (h - 1) // 2 + 1, (w - 1) // 2 + 1
+
+
+def check_blur(C: int, H: int, W: int) -> None:
+    if C < 64 or C % 64 or H < 2 or W < 2:
+        raise ValueError(f"the blur kernels take C % 64 == 0 and a feature map of at least 2 x 2; got C={C}, "
+                         f"{H} x {W}")
+
+
+def _blur(x):
+    """blur of an NHWC tensor, in its dtype."""
+    C = x.shape[-1]
+    k = torch.tensor([1.0, 2.0, 1.0], dtype=x.dtype, device=x.device)
+    w = (k[:, None] * k[None, :] / 16).expand(C, 1, 3, 3)
+    return _nhwc(F.conv2d(F.pad(_nchw(x), (1, 1, 1, 1), mode="reflect"), w, stride=2, groups=C))
+
+
+def _blur_t(d, H: int, W: int):
+    """blur^T of an NHWC gradient (fp32), for an input of H x W: the vector-Jacobian product of :func:`_blur`."""
+    x = torch.zeros(d.shape[0], H, W, d.shape[-1], dtype=torch.float32, device=d.device)
+    return torch.autograd.functional.vjp(_blur, x, d.float())[1]
+
+
+def blur_fwd(y, out, *, scale=None, shift=None, relu=True):
+    check_blur(y.shape[-1], y.shape[1], y.shape[2])
+    a = y.float()
+    if scale is not None:
+        a = a * scale + shift
+        if relu:
+            a = torch.relu(a)
+    out.copy_(_blur(a).bfloat16())
+    return out
+
+
+def blur_bwd(dout, dx):
+    check_blur(dx.shape[-1], dx.shape[1], dx.shape[2])
+    dx.copy_(_blur_t(dout, dx.shape[1], dx.shape[2]).bfloat16())
+
+
+def _blur_g(dpool, y, scale, shift):
+    g = _blur_t(dpool, y.shape[1], y.shape[2])
+    return torch.where(y.float() * scale + shift > 0, g, torch.zeros_like(g))
+
+
+def blur_bn_bwd_reduce(dpool, y, scale, shift, mean, invstd, stats):
+    C = y.shape[-1]
+    check_blur(C, y.shape[1], y.shape[2])
+    g = _blur_g(dpool, y, scale, shift).reshape(-1, C)
+    xhat = ((y.float() - mean) * invstd).reshape(-1, C)
+    st = stats.view(-1, 2, C)
+    st[0, 0] += g.sum(0).double()
+    st[0, 1] += (g * xhat).sum(0).double()
+
+
+def blur_bn_bwd_apply(dpool, y, scale, shift, coeff, dy):
+    C = y.shape[-1]
+    check_blur(C, y.shape[1], y.shape[2])
+    g = _blur_g(dpool, y, scale, shift)
+    k = coeff.view(3, C)
+    dy.copy_((k[0] * g + k[1] * y.float() + k[2]).bfloat16())
+
+
 def stem_bwd_fused(dpool, arg, y, scale, shift, coeff, x4, dw, ws, *, K=3, stride=2, pad=1, R=7, S=7,
                    conv_stride=2, conv_pad=3):
     """Fused stem backward = pool_bn_bwd_apply + the stem weight gradient."""
