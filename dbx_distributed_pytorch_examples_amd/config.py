@@ -272,6 +272,13 @@ def validate_drop_path(rate: Any) -> float:
     return float(rate)
 
 
+def validate_drop_block(rate: Any) -> float:
+    """ValueError unless the DropBlock rate is a number in [0, 1). Shared by the config and the trainers."""
+    if isinstance(rate, bool) or not isinstance(rate, (int, float)) or not 0.0 <= float(rate) < 1.0:
+        raise ValueError(f"drop_block_rate must be a number in [0, 1), got {rate!r}")
+    return float(rate)
+
+
 def drop_path_probs(rate: float, nblocks: int) -> List[float]:
     """timm's linear stochastic-depth rule over ``nblocks`` residual blocks: p_l = rate * l / (L - 1), in
     float64 (Python floats). The first block is never dropped, the last one with probability ``rate``."""
@@ -287,6 +294,7 @@ def validate_train(cfg: "TrainConfig") -> None:
     """ValueError for a bad data setting (:func:`validate_data`) or stochastic-depth rate."""
     validate_data(cfg.data)
     validate_drop_path(cfg.drop_path_rate)
+    validate_drop_block(cfg.drop_block_rate)
 
 
 @dataclass
@@ -301,6 +309,10 @@ class TrainConfig:
     # stochastic depth, per batch (native engine): block l of L is dropped for a whole micro-batch with probability
     # rate * l / (L - 1) and scaled by 1 / (1 - p_l) otherwise (timm's linear rule; A1 / A2 use 0.05). In [0, 1).
     drop_path_rate: float = 0.0
+    # DropBlock (native engine: Philox block masks inside the captured step; autograd engine: the torch module): every
+    # block of layer3 (block size 5, gamma scale 0.25) and layer4 (3, 1.0) drops bs x bs blocks per sample and channel
+    # behind its 3x3 conv's BN (timm's drop_block_rate; the paper uses 0.1). In [0, 1); passed to the model build.
+    drop_block_rate: float = 0.0
     epochs: int = 1
     max_steps: int = 0                 # 0 = full epochs
     duration: str = ""                 # composer style: "2ep" / "100ba"

@@ -198,5 +198,26 @@ struct SeArgs {
   int N, HW, C, rd, nsplit, nshard, res_mode, pad_;
 };
 static_assert(sizeof(SeArgs) == 32 * 8 + 8 * 4, "ops/kernels.py packs SeArgs as 32 pointers + 8 int32");
+// DropBlock kernels (dropblock_ops.hip). One table for all of them: Python packs it as 16 pointers, the 64-bit seed
+// and 8 int32 (ops/kernels.py _dropblock_launch), each kernel reads the fields it needs, the rest are null.
+struct DropBlockArgs {
+  const bf16* y;                // the BN input [N][H][W][C]
+  const bf16* d;                // gradient of the masked activation (backward forms)
+  bf16* out;                    // dropblock_fwd: the masked activation; the apply form: dy
+  unsigned* bits;               // the keep mask, [N][H][W][C/32], bit c % 32
+  const float* sc;              // the BN's forward scale / shift [C]
+  const float* sh;
+  const float* c1;              // reduce: mean, invstd; apply: bn_bwd_coeff's k1, k2, k3
+  const float* c2;
+  const float* c3;
+  double* stats;                // reduce: the BN's backward moments [nshard][2][C]
+  unsigned long long* kept;     // the site's counter of kept elements (zeroed before dropblock_mask adds to it)
+  const unsigned* thr;          // the site's seed threshold: seed iff Philox word < *thr
+  const unsigned* offset;       // the Philox offset, read on the device
+  const void* rsv_[3];
+  unsigned long long seed;
+  int N, H, W, C, bs, site, nshard, pad_;
+};
+static_assert(sizeof(DropBlockArgs) == 16 * 8 + 8 + 8 * 4, "ops/kernels.py packs DropBlockArgs by byte offset");
 
 }  // namespace dbx

@@ -188,6 +188,16 @@ PYBIND11_MODULE(_C, m) {
           "wgrad_reduce_multi_plan");
     return std::make_pair(ga, gb);
   });
+  // dropout with its trailing arguments defaulted (a nonzero dropblock_op: dbx_dropblock_op on the packed
+  // DropBlockArgs at dropblock_args -- the module exports the names it exported)
+  m.def("dropout", [](uintptr_t x, uintptr_t y, long long n, unsigned long long seed, unsigned offset, unsigned thresh,
+                      float inv_keep, uintptr_t offset_dev, uintptr_t st, int dropblock_op, uintptr_t dropblock_args) {
+    check(dbx_dropout(reinterpret_cast<const bf16*>(x), reinterpret_cast<bf16*>(y), n, seed, offset, thresh, inv_keep,
+                      reinterpret_cast<const unsigned*>(offset_dev), stream(st), dropblock_op,
+                      reinterpret_cast<const dbx::DropBlockArgs*>(dropblock_args)),
+          "dropout");
+  }, "x"_a, "y"_a, "n"_a, "seed"_a, "offset"_a, "thresh"_a, "inv_keep"_a, "offset_dev"_a, "st"_a,
+     "dropblock_op"_a = 0, "dropblock_args"_a = 0);
   m.def("wgrad_reduce_job_bytes", []() { return dbx_wgrad_reduce_job_bytes(); });
   m.def("mnist_saved_bytes", []() { return dbx_mnist_saved_bytes(); });
 
@@ -232,6 +242,5 @@ PYBIND11_MODULE(_C, m) {
   DBX_BIND(mnist_fwd);
   DBX_BIND(mnist_bwd);
   DBX_BIND(colsum);
-  DBX_BIND(dropout);
   m.attr("arch") = "gfx950";
 }

@@ -162,8 +162,19 @@ int dbx_blur_op(int op, const bf16* a, const bf16* y, const float* sc, const flo
 // ---- classifier head (head_ops.hip) -----------------------------------------------------------------------------
 int dbx_small_gemm(int ta, int tb, int out_f32, int drop, const dbx::GemmArgs* args, hipStream_t st);
 int dbx_colsum(const bf16* X, float* out, int M, int N, int accumulate, hipStream_t st);
+// dropblock_op != 0: the DropBlock kernels instead -- forwards to dbx_dropblock_op(dropblock_op, dropblock_args) below;
+// the tensors and the draw's parameters are then unread
 int dbx_dropout(const bf16* x, bf16* y, long long n, unsigned long long seed, unsigned offset, unsigned thresh,
-                float inv_keep, const unsigned* offset_dev, hipStream_t st);
+                float inv_keep, const unsigned* offset_dev, hipStream_t st, int dropblock_op = 0,
+                const dbx::DropBlockArgs* dropblock_args = nullptr);
+
+// ---- DropBlock (dropblock_ops.hip) ----------------------------------------------------------------------------------
+// a site behind a BN on [N,H,W,C], C % 64 == 0, block size 1..7 (clipped to the map, made odd), N <= 65535.
+// op 1 dropblock_mask: bits = the Philox block mask (bit c % 32 of word [n,h,w,c/32] = keep), *kept += its ones;
+// op 2 dropblock_fwd: out = relu(y*sc + sh) * keep * scale, scale = N*H*W*C / max(*kept, 1); op 3 / 4
+// dropblock_bn_bwd reduce / apply: g = d * keep * scale * [y*sc + sh > 0], stats += [sum g, sum g * (y - c1) * c2] /
+// out = c1*g + c2*y + c3. *args is a HOST struct (abi.h). Python reaches it through dropout's binding
+int dbx_dropblock_op(int op, const dbx::DropBlockArgs* args, hipStream_t st);
 
 // ---- fused MNIST Net, one workgroup per image (mnist_ops.hip) -----------------------------------------------------
 long long dbx_mnist_saved_bytes();

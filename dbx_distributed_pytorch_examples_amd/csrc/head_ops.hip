@@ -272,7 +272,9 @@ extern "C" int dbx_colsum(const bf16* X, float* out, int M, int N, int accumulat
 }
 
 extern "C" int dbx_dropout(const bf16* x, bf16* y, long long n, unsigned long long seed, unsigned offset,
-                           unsigned thresh, float inv_keep, const unsigned* offset_dev, hipStream_t st) {
+                           unsigned thresh, float inv_keep, const unsigned* offset_dev, hipStream_t st,
+                           int dropblock_op, const dbx::DropBlockArgs* dropblock_args) {
+  if (dropblock_op != 0) return dropblock_args ? dbx_dropblock_op(dropblock_op, dropblock_args, st) : -91;
   long long blocks = (n + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)blocks), dim3(256), 0, st, x, y, n, seed, offset, thresh, inv_keep,

@@ -167,6 +167,9 @@ class FrozenFeatureTrainer:
         if src_ragged is not None:  # refused, never ignored
             raise ValueError(f"src_ragged={src_ragged!r} needs the native training step (NativeTrainer); the "
                              f"frozen-backbone trainer takes dense [N, Hs, Ws, C] batches (src_hw)")
+        if any(type(m).__name__ == "DropBlock2d" for m in model.modules()):  # refused, never ignored
+            raise ValueError("drop_block_rate needs the native training step (NativeTrainer); the frozen backbone runs "
+                             "in evaluation mode and drops nothing")
         if validate_drop_path(drop_path_rate) != 0.0:  # refused, never ignored
             raise ValueError(f"drop_path_rate={drop_path_rate!r} needs the native training step (NativeTrainer); the "
                              f"frozen-backbone trainer runs its backbone in evaluation mode, which never drops a block")

@@ -318,6 +318,9 @@ def native_module(model: nn.Module, batch: Optional[int] = None, image_hw: Optio
     if src_ragged is not None:  # refused, never ignored
         raise ValueError(f"src_ragged={src_ragged!r} needs the native training step (NativeTrainer), whose input "
                          f"kernels crop every image from its own size; native_module takes dense float batches")
+    if any(type(m).__name__ == "DropBlock2d" for m in model.modules()):  # refused, never ignored
+        raise ValueError("a model with DropBlock2d sites needs the native training step (NativeTrainer), whose "
+                         "captured step advances the mask offset; native_module runs no such step")
     if validate_drop_path(drop_path_rate) != 0.0:  # refused, never ignored
         raise ValueError(f"drop_path_rate={drop_path_rate!r} needs the native training step (NativeTrainer), which "
                          f"draws the per-batch gates each step; native_module has no per-step host stage")

@@ -32,7 +32,7 @@ import torch.distributed as dist
 import torch.nn as nn
 
 from ..config import (distinct_param_groups, drop_path_probs, has_param_groups, resolve_param_groups,
-                      validate_drop_path, validate_loss)
+                      validate_drop_block, validate_drop_path, validate_loss)
 from ..engine_config import EngineConfig
 from ..ops import kernels as K
 from ..parallel.dist import host_sync_for_gloo
@@ -89,8 +89,9 @@ class NativeTrainer:
                  bce_target_threshold: Optional[float] = None, bce_sum_classes: bool = False,
                  ra_num_ops: int = 2, ra_magnitude: int = 9, drop_path_rate: float = 0.0,
                  src_ragged: Optional[Tuple[int, int]] = None, resample: Optional[str] = None,
-                 eval_resample: Optional[str] = None):
+                 eval_resample: Optional[str] = None, drop_block_rate: float = 0.0):
         validate_loss(loss, bce_target_threshold, bce_sum_classes)
+        self.drop_block_rate = validate_drop_block(drop_block_rate)
         # resample / eval_resample (None = resample): the crop-resize filter of the input kernels in training and
         # in evaluation -- "aa_bilinear", "bicubic", "aa_bicubic" (K.augment_u8); None: the two-tap bilinear kernels.
         # With mixing or erasing the filtered uint8 batch goes through K.trivial_augment_u8 (an Identity table when
@@ -205,6 +206,18 @@ class NativeTrainer:
             self._drop_p = np.array([self.drop_path_p[l] for l in self.prog.drop_blocks], dtype=np.float64)
             self._drop_keep = (1.0 / (1.0 - self._drop_p)).astype(np.float32)
             self._drop_dev = DeviceHyper(self.prog.drop_gates)
+        # DropBlock (ResNetProgram: the model's DropBlock2d sites): the masks are drawn on the device from Philox(seed
+        # and rank, an offset the step advances), so nothing is sampled here; drop_block_rate > 0 overrides the rate
+        # the model was built with, and is refused for a model without sites
+        if self.prog.db_blocks:
+            self.prog.db_seed = rng_seed
+            if self.drop_block_rate > 0:
+                self.prog.set_drop_block_rate(self.drop_block_rate)
+            else:  # (the rate the model was built with)
+                self.drop_block_rate = self.prog.db_blocks[0].db_mod.drop_prob
+        elif self.drop_block_rate > 0:
+            raise ValueError(f"drop_block_rate={drop_block_rate!r}: the model has no DropBlock2d sites; build it with "
+                             f"build_model(name, drop_block_rate=...)")
         n = self.prog.n_params
         self.mom = torch.zeros(n, device=device)
         self.mom2 = torch.zeros(n, device=device) if optim.name in ("adam", "adamw", "lamb") else None
@@ -703,6 +716,24 @@ class NativeTrainer:
         self.last_drop_path = {"p": self._drop_p.tolist(), "gates": [float(g) for g in gates],
                                "dropped": [l for l, d in zip(self.prog.drop_blocks, dropped) if d]}
         self._drop_dev.set(self.last_drop_path["gates"])
+
+    def set_drop_block_rate(self, p: float) -> None:
+        """Ramp the DropBlock rate: the sites' seed thresholds are rewritten on the device, so the next step -- a
+        replay of the captured graph included -- draws its masks with ``p``."""
+        self.drop_block_rate = validate_drop_block(p)
+        self.prog.set_drop_block_rate(self.drop_block_rate)
+
+    @property
+    def last_drop_block(self) -> List[dict]:
+        """Per site the ``kept`` count and ``scale`` of the last step's mask (read back on demand)."""
+        return self.prog.drop_block_state()
+
+    def drop_block_summary(self) -> dict:
+        """The DropBlock settings and the last step's masks, for logging."""
+        sites = self.prog.db_blocks
+        return {"drop_block_rate": self.drop_block_rate, "sites": len(sites),
+                "block_sizes": sorted({b.db_cfg[0] for b in sites}), "kernel": "dropblock_mask" if sites else None,
+                "launches_per_step": 4 * len(sites), "last": self.last_drop_block}
 
     def drop_path_summary(self) -> dict:
         """The stochastic-depth settings, for logging."""

@@ -37,7 +37,8 @@ import torch
 import torch.nn as nn
 
 from ..engine_config import EngineConfig
-from ..models.resnet import BasicBlock, BlurPool2d, Bottleneck, CifarBlock, CifarResNet18, ResNet, SEModule
+from ..models.resnet import (BasicBlock, BlurPool2d, Bottleneck, CifarBlock, CifarResNet18, DropBlock2d, ResNet,
+                             SEModule)
 from ..ops import kernels as K
 from .schedule import ScheduleContext, StepSchedule, resolve_schedule
 
@@ -186,6 +187,14 @@ class BlockL:
     # blurred tensor, the plain operand of conv j + 1), None without one; blur_hw = ((H, W) before, (P, Q) behind)
     blur: Optional[int] = None
     blur_hw: Optional[Tuple[Tuple[int, int], Tuple[int, int]]] = None
+    # DropBlock: the index j of the conv behind whose BN a DropBlock2d sits (training: acts[j] is the masked, scaled
+    # BN + ReLU output, the plain operand of conv j + 1), None without one; db_cfg = (block size, gamma scale, site),
+    # db_bits the packed keep mask int32 [N, H, W, C / 32], db_mat0 what mat[j] would be without the site (evaluation)
+    dropblock: Optional[int] = None
+    db_cfg: Optional[Tuple[int, float, int]] = None
+    db_mod: Optional[DropBlock2d] = None
+    db_bits: Optional[torch.Tensor] = None
+    db_mat0: bool = False
 
 
 class ResNetProgram:
@@ -347,6 +356,17 @@ class ResNetProgram:
                             f"{H} x {W}")
         return (H, W), K.blur_out_hw(H, W)
 
+    def _dropblock(self, name: str, mod, conv: ConvL, site: int, blurred: bool) -> Tuple[int, float, int]:
+        """A DropBlock2d behind ``conv``'s BN: (block size, gamma scale, site)."""
+        if not isinstance(mod, DropBlock2d):
+            raise TypeError(f"{name}: unsupported regulariser (a models.DropBlock2d is expected)")
+        if blurred:
+            raise TypeError(f"{name}: a block with both a BlurPool2d and a DropBlock2d is not built")
+        if not K.dropblock_supported(conv.OC, conv.OH, conv.OW, mod.block_size) or self.N > 65535:
+            raise TypeError(f"{name}: the DropBlock kernels take C % 64 == 0, a block size in 1..7 and at most 65535 "
+                            f"images, got C={conv.OC}, block size {mod.block_size}, batch {self.N}")
+        return mod.block_size, mod.gamma_scale, site
+
     def _build_layers(self):
         m = self.model
         self.stem = self._conv("conv1", m.conv1, self.H, self.W, stem=True)
@@ -416,6 +436,11 @@ class ResNetProgram:
                         raise TypeError(f"{pre}: the shortcut and the blurred branch give different sizes")
                 if getattr(blk, "se", None) is not None:
                     blk_l.se = self._se(f"{pre}.se", blk.se, last.OC)
+                if getattr(blk, "drop_block", None) is not None:
+                    nsite = sum(bb.dropblock is not None for bb in self.blocks)
+                    blk_l.dropblock, blk_l.db_mod = len(convs) - 2, blk.drop_block
+                    blk_l.db_cfg = self._dropblock(f"{pre}.drop_block", blk.drop_block, convs[-2], nsite,
+                                                   bhw is not None)
                 self.blocks.append(blk_l)
                 h, w, c = last.OH, last.OW, last.OC
         self.feat_hw = (h, w)
@@ -620,11 +645,17 @@ class ResNetProgram:
             # reads them instead of re-applying BN+ReLU to every staged tile
             # (the input of a grouped conv, or of one wider than the BN prologue holds, is always materialised)
             # (and so is the blurred tensor, which only the forward can compute)
-            b.acts = [E(N, *ahw[j], cv.OC) if (self.act_writeback or self._plain_only(b.convs[j + 1]) or j == b.blur)
+            # (and the masked tensor behind a DropBlock site)
+            b.acts = [E(N, *ahw[j], cv.OC) if (self.act_writeback or self._plain_only(b.convs[j + 1]) or j == b.blur
+                                               or j == b.dropblock)
                       else None for j, cv in enumerate(b.convs[:-1])]
             # acts[j] computed in the forward (eight-wave or grouped consumer conv j+1): see self.fast_mat
             b.mat = [j == b.blur or (self._materialize(b.convs[j + 1]) and b.acts[j] is not None)
                      for j in range(len(b.convs) - 1)]
+            if b.dropblock is not None:
+                j, cv = b.dropblock, b.convs[b.dropblock]
+                b.db_mat0, b.mat[j] = b.mat[j], True
+                b.db_bits = torch.empty(N, cv.OH, cv.OW, cv.OC // 32, device=dev, dtype=torch.int32)
             h, w, c = b.in_shape
             b.dx = E(N, h, w, c)
             if b.ds_conv is not None:
@@ -642,6 +673,17 @@ class ResNetProgram:
         # SE blocks: the per-sample tables, one masked-gradient scratch buffer for all of them (a block's shortcut
         # add is its last reader) and the partial sums of the split reductions
         self.se_g = self.se_ws = None
+        # DropBlock sites: a counter of kept elements and a uint32 seed threshold per site, and the Philox offset they
+        # share. The step's weight-prep launch zeroes the counters and advances the offset (_pack_step_descs)
+        self.db_blocks = [b for b in self.blocks if b.dropblock is not None]
+        self.db_kept = self.db_thr = self.db_off = self._db_ctr = None
+        self.db_seed = 0
+        if self.db_blocks:
+            self.db_kept = torch.zeros(len(self.db_blocks), device=dev, dtype=torch.int64)
+            self.db_thr = torch.zeros(len(self.db_blocks), device=dev, dtype=torch.int32)
+            self._db_ctr = torch.zeros(1, device=dev, dtype=torch.int64)
+            self.db_off = self._db_ctr.view(torch.int32)[0:1]
+            self.set_drop_block_rate(None)
         if self.ses:
             f32 = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)  # noqa: E731
             z16 = lambda *s: torch.zeros(*s, device=dev, dtype=bf)  # noqa: E731
@@ -746,6 +788,9 @@ class ResNetProgram:
             extra.append((self.nbt.data_ptr(), 0, -4, self.nbt.numel(), 0, 0))
         if self._erase_ctr is not None:  # the erase noise's Philox offset: + 1 per step, on the device
             extra.append((self._erase_ctr.data_ptr(), 0, -4, 1, 0, 0))
+        if self.db_kept is not None:  # DropBlock: the sites' counters start at 0, the mask offset advances
+            extra.append((self.db_kept.data_ptr(), 0, -3, self.db_kept.numel(), 0, 0))
+            extra.append((self._db_ctr.data_ptr(), 0, -4, 1, 0, 0))
         self.wdesc_step = self._pack_wdesc(self._wdescs + extra) if self.dev.type == "cuda" else None
         self.n_wdesc_step = len(self._wdescs) + len(extra)
         self._stats_zeroed = False
@@ -867,6 +912,33 @@ class ResNetProgram:
         self.mix_lam = torch.ones(1, device=dev, dtype=torch.float32)
         self.labels2 = torch.zeros(self.N, device=dev, dtype=torch.int64)
 
+    def set_drop_block_rate(self, p: Optional[float]) -> None:
+        """Rewrite the sites' seed thresholds for drop probability ``p`` (None: every site's own ``drop_prob``): a
+        host-side write into the device table, so the next replay of a captured step follows it."""
+        if not self.db_blocks:
+            raise RuntimeError("set_drop_block_rate: the model has no DropBlock sites")
+        if p is not None and not 0.0 <= p < 1.0:
+            raise ValueError(f"drop_block_rate must be in [0, 1), got {p}")
+        thr = []
+        for b in self.db_blocks:
+            cv, (bs, gs, _) = b.convs[b.dropblock], b.db_cfg
+            gamma = K.dropblock_geometry(cv.OH, cv.OW, bs, b.db_mod.drop_prob if p is None else p, gs)[1]
+            t = K.dropblock_threshold(gamma)
+            thr.append(t - (1 << 32) if t >= (1 << 31) else t)  # (the uint32's bits in an int32 table)
+        self.db_thr.copy_(torch.tensor(thr, dtype=torch.int32))
+
+    def drop_block_state(self) -> List[dict]:
+        """Per site what the last training forward drew: kept elements and the scale (reads the device: not for the
+        inside of a captured step)."""
+        kept = self.db_kept.tolist() if self.db_kept is not None else []
+        out = []
+        for b, k in zip(self.db_blocks, kept):
+            cv = b.convs[b.dropblock]
+            numel = self.N * cv.OH * cv.OW * cv.OC
+            out.append({"site": b.db_cfg[2], "block": cv.name.rsplit(".", 1)[0], "numel": numel, "kept": int(k),
+                        "scale": K.dropblock_scale(numel, k)})
+        return out
+
     def enable_drop_path(self, probs) -> None:
         """Stochastic depth, per batch (Huang et al. 2016; ``torchvision.ops.stochastic_depth(mode="batch")``):
         ``probs[l]`` is block l's drop probability, and every block with ``probs[l] > 0`` gets a gate -- a scalar
@@ -944,6 +1016,9 @@ class ResNetProgram:
             self.nbt.add_(1)
             if self._erase_ctr is not None:
                 self._erase_ctr.add_(1)
+            if self.db_kept is not None:
+                self.db_kept.zero_()
+                self._db_ctr.add_(1)
 
     def bn_param_blocks(self) -> List[Tuple[int, int]]:
         """Contiguous [lo, hi) blocks of the flat buffer holding the parameters the kernels read in fp32
@@ -1057,11 +1132,23 @@ class ResNetProgram:
                     K.blur_fwd(b.ys[i - 1], b.acts[i - 1], scale=prev_bn.scale, shift=prev_bn.shift, relu=True)
                     K.conv_fwd(b.acts[i - 1], cv.w16, b.ys[i], R=cv.R, S=cv.S, stride=cv.stride, pad=cv.pad,
                                stats=b.bns[i].stats if tr else None, fin=self._ff(b.bns[i]))
+                elif tr and i > 0 and b.dropblock == i - 1:
+                    # a fresh block mask (csrc/dropblock_ops.hip), then BN + ReLU + mask + scale in one pass: the
+                    # masked tensor is this conv's plain operand (and its weight gradient's)
+                    s = b.db_cfg[2]
+                    K.dropblock_mask(b.db_bits, self.db_kept[s:s + 1], self.db_thr[s:s + 1], self.db_off,
+                                     block_size=b.db_cfg[0], seed=self.db_seed, site=s)
+                    K.dropblock_fwd(b.ys[i - 1], prev_bn.scale, prev_bn.shift, b.db_bits, self.db_kept[s:s + 1],
+                                    b.acts[i - 1])
+                    K.conv_fwd(b.acts[i - 1], cv.w16, b.ys[i], R=cv.R, S=cv.S, stride=cv.stride, pad=cv.pad,
+                               stats=b.bns[i].stats if tr else None, fin=self._ff(b.bns[i]))
                 elif i > 0 and cv.groups > 1:  # materialised BN output -> grouped 3x3 (csrc/conv_group.hip)
                     K.bn_apply(b.ys[i - 1], prev_bn.scale, prev_bn.shift, b.acts[i - 1], relu=True)
                     K.group_conv_fwd(b.acts[i - 1], cv.w16, b.ys[i], groups=cv.groups, stride=cv.stride,
                                      stats=b.bns[i].stats if tr else None)
-                elif i > 0 and b.mat[i - 1]:  # materialised BN output -> plain-operand (eight-wave) conv
+                elif i > 0 and (b.mat[i - 1] if b.dropblock != i - 1 else b.db_mat0):
+                    # materialised BN output -> plain-operand (eight-wave) conv (a DropBlock site in evaluation: the
+                    # route the block takes without it)
                     K.bn_apply(b.ys[i - 1], prev_bn.scale, prev_bn.shift, b.acts[i - 1], relu=True)
                     K.conv_fwd(b.acts[i - 1], cv.w16, b.ys[i], R=cv.R, S=cv.S, stride=cv.stride, pad=cv.pad,
                                stats=b.bns[i].stats if tr else None, fin=self._ff(b.bns[i]))
@@ -1427,7 +1514,8 @@ class ResNetProgram:
         pend, gin = None, None  # BN-backward apply deferred into the next dgrad's prologue
         ds_fold = None  # ... and the downsample BN's, into the downsample dgrad
         fuse3 = self._fuse3(b, last)  # conv3's BN-backward apply + dgrad + wgrad in one kernel
-        fold_lc = b.blur is None and self._fold(lc)  # (nothing is folded into the conv behind a blur)
+        # (nothing is folded into the conv behind a blur or a DropBlock site)
+        fold_lc = b.blur is None and b.dropblock is None and self._fold(lc)
         if b.se is not None:
             g = self._bwd_se_tail(b, self.dlast if last else self.blocks[i + 1].dx)
         elif last:
@@ -1509,6 +1597,20 @@ class ResNetProgram:
                 K.blur_bn_bwd_reduce(b.das[j - 1], b.ys[j - 1], pbn.scale, pbn.shift, pbn.mean, pbn.invstd, pbn.bstats)
                 self._coeff(pbn, N * pc.OH * pc.OW)
                 K.blur_bn_bwd_apply(b.das[j - 1], b.ys[j - 1], pbn.scale, pbn.shift, pbn.coeff, b.dys[j - 1])
+                continue
+            if b.dropblock == j - 1:
+                # the conv behind a DropBlock site: its data gradient is the gradient of the masked tensor (no mask
+                # epilogue); the block mask, its scale, the ReLU mask and the BN backward are one reduce / apply pair
+                assert not kw, "nothing is folded into the conv behind a DropBlock site"
+                s = b.db_cfg[2]
+                kept = self.db_kept[s:s + 1]
+                K.conv_dgrad(src, cv.wt16, b.das[j - 1], R=cv.R, S=cv.S, stride=cv.stride, pad=cv.pad)
+                self._wgrad(b.dys[j], act, cv.grad, self.ws, R=cv.R, S=cv.S, stride=cv.stride, pad=cv.pad)
+                K.dropblock_bn_bwd_reduce(b.das[j - 1], b.ys[j - 1], pbn.scale, pbn.shift, b.db_bits, kept, pbn.mean,
+                                          pbn.invstd, pbn.bstats)
+                self._coeff(pbn, N * pc.OH * pc.OW)
+                K.dropblock_bn_bwd_apply(b.das[j - 1], b.ys[j - 1], pbn.scale, pbn.shift, b.db_bits, kept, pbn.coeff,
+                                         b.dys[j - 1])
                 continue
             if cv.groups > 1:
                 # grouped conv2: plain data gradient, then the ReLU mask and BN1's backward as standalone passes
@@ -1633,7 +1735,8 @@ class ResNetProgram:
     def _fuse3(self, b: BlockL, last: bool) -> bool:
         """Run block b's conv3 backward through K.conv_dwfused (the 64 -> 256 conv3 of the 56x56
         stage: its weight-gradient accumulators fit a workgroup's registers)."""
-        if not self.fuse_dw or last or b.kind != "bottleneck" or b.se is not None or b.blur is not None:
+        if (not self.fuse_dw or last or b.kind != "bottleneck" or b.se is not None or b.blur is not None
+                or b.dropblock is not None):
             return False
         c3 = b.convs[-1]
         return ((c3.R, c3.S, c3.stride, c3.pad) == (1, 1, 1, 0) and c3.OH >= self.cfg.fuse_dw_min_hw

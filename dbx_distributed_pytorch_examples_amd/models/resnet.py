@@ -25,7 +25,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 __all__ = [
-    "BasicBlock", "BlurPool2d", "Bottleneck", "ResNet", "SEModule", "resnetblur18", "resnetblur34", "resnetblur50",
+    "BasicBlock", "BlurPool2d", "Bottleneck", "DropBlock2d", "ResNet", "SEModule", "resnetblur18", "resnetblur34", "resnetblur50",
     "resnetblur101", "seresnet18", "seresnet34", "seresnet50", "seresnet101",
     "seresnet152", "seresnext50_32x4d", "seresnext101_32x8d", "resnet18", "resnet34", "resnet50",
     "resnet101", "resnet152", "resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d", "wide_resnet50_2",
@@ -74,16 +74,57 @@ class BlurPool2d(nn.Module):
                         groups=self.channels)
 
 
+class DropBlock2d(nn.Module):
+    """DropBlock (Ghiasi et al. 2018) as timm's ``drop_block_2d`` with ``batchwise=False, with_noise=False``: in
+    training, seeds are drawn per sample and channel with probability ``gamma`` inside the valid interior of the map,
+    every ``bs x bs`` window around a seed is zeroed and the rest is scaled by ``numel / max(kept, 1)``; ``bs`` is
+    ``block_size`` clipped to the map and made odd. The identity in evaluation. No parameters and no buffers.
+    The seeds come from torch's generator, or -- when the attribute ``philox = (seed, offset, site)`` is set -- from
+    the counter-based mask of the native step (``ops.reference.dropblock_mask``), element for element."""
+
+    def __init__(self, drop_prob: float = 0.1, block_size: int = 7, gamma_scale: float = 1.0):
+        super().__init__()
+        if not 0.0 <= drop_prob < 1.0:
+            raise ValueError(f"drop_prob must be in [0, 1), got {drop_prob}")
+        if block_size < 1:
+            raise ValueError(f"block_size must be at least 1, got {block_size}")
+        self.drop_prob, self.block_size, self.gamma_scale = float(drop_prob), int(block_size), float(gamma_scale)
+        self.philox = None
+
+    def extra_repr(self) -> str:
+        return f"drop_prob={self.drop_prob}, block_size={self.block_size}, gamma_scale={self.gamma_scale}"
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if not self.training or self.drop_prob == 0.0:
+            return x
+        from ..ops import reference as R
+        N, C, H, W = x.shape
+        bs, gamma = R.dropblock_geometry(H, W, self.block_size, self.drop_prob, self.gamma_scale)
+        if self.philox is not None:
+            seed, offset, site = self.philox[:3]
+            bits, kept = R.dropblock_mask(N, H, W, C, R.dropblock_threshold(gamma), bs, int(seed), int(offset), int(site))
+            keep = R.dropblock_unpack(bits, C).permute(0, 3, 1, 2).to(x.device)
+        else:
+            r = bs // 2
+            seeds = torch.zeros(N, C, H, W, device=x.device)
+            seeds[:, :, r:H - r, r:W - r] = (torch.rand(N, C, H - 2 * r, W - 2 * r, device=x.device) < gamma).float()
+            keep = 1.0 - F.max_pool2d(seeds, bs, 1, r)
+            kept = int(keep.sum())
+        return x * (keep * R.dropblock_scale(N * C * H * W, kept)).to(x.dtype)
+
+
 class BasicBlock(nn.Module):
     """torchvision BasicBlock (two 3x3 convs), keys conv1/bn1/conv2/bn2/downsample.{0,1}. ``se_reduction`` > 0: an
     :class:`SEModule` ``se`` gates the output of bn2 before the shortcut add (timm's seresnet18 / 34).
     ``blur_pool`` (timm's resnetblur18): a stride-2 block runs conv1 at stride 1 and a :class:`BlurPool2d` ``blur``
-    down-samples behind bn1 + ReLU; the shortcut is unchanged."""
+    down-samples behind bn1 + ReLU; the shortcut is unchanged. ``drop_block_rate`` > 0: a :class:`DropBlock2d`
+    ``drop_block`` of ``drop_block_size`` / ``drop_block_gamma`` sits behind bn1, in front of its ReLU (timm)."""
 
     expansion = 1
 
     def __init__(self, inplanes: int, planes: int, stride: int = 1,
-                 downsample: Optional[nn.Module] = None, se_reduction: int = 0, blur_pool: bool = False):
+                 downsample: Optional[nn.Module] = None, se_reduction: int = 0, blur_pool: bool = False,
+                 drop_block_rate: float = 0.0, drop_block_size: int = 3, drop_block_gamma: float = 1.0):
         super().__init__()
         blur = blur_pool and stride == 2
         self.conv1 = conv3x3(inplanes, planes, 1 if blur else stride)
@@ -95,12 +136,18 @@ class BasicBlock(nn.Module):
             self.se = SEModule(planes, se_reduction)
         if blur:  # (likewise)
             self.blur = BlurPool2d(planes, stride)
+        if drop_block_rate > 0:  # (likewise)
+            self.drop_block = DropBlock2d(drop_block_rate, drop_block_size, drop_block_gamma)
         self.downsample = downsample
         self.stride = stride
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         identity = x
-        out = self.relu(self.bn1(self.conv1(x)))
+        out = self.bn1(self.conv1(x))
+        drop = getattr(self, "drop_block", None)
+        if drop is not None:
+            out = drop(out)
+        out = self.relu(out)
         blur = getattr(self, "blur", None)
         if blur is not None:
             out = blur(out)
@@ -118,13 +165,15 @@ class Bottleneck(nn.Module):
     (ResNeXt, Wide ResNet): the inner width is ``int(planes * base_width / 64) * groups`` and the 3x3 conv is grouped.
     ``se_reduction`` > 0: an :class:`SEModule` ``se`` gates the output of bn3 before the shortcut add (SE-ResNet).
     ``blur_pool`` (timm's resnetblur50): a stride-2 block runs conv2 at stride 1 and a :class:`BlurPool2d` ``blur``
-    down-samples behind bn2 + ReLU; the shortcut is unchanged."""
+    down-samples behind bn2 + ReLU; the shortcut is unchanged. ``drop_block_rate`` > 0: a :class:`DropBlock2d`
+    ``drop_block`` of ``drop_block_size`` / ``drop_block_gamma`` sits behind bn2, in front of its ReLU (timm)."""
 
     expansion = 4
 
     def __init__(self, inplanes: int, planes: int, stride: int = 1,
                  downsample: Optional[nn.Module] = None, groups: int = 1, base_width: int = 64,
-                 se_reduction: int = 0, blur_pool: bool = False):
+                 se_reduction: int = 0, blur_pool: bool = False, drop_block_rate: float = 0.0,
+                 drop_block_size: int = 3, drop_block_gamma: float = 1.0):
         super().__init__()
         width = int(planes * base_width / 64) * groups
         blur = blur_pool and stride == 2
@@ -138,6 +187,8 @@ class Bottleneck(nn.Module):
             self.se = SEModule(planes * self.expansion, se_reduction)
         if blur:
             self.blur = BlurPool2d(width, stride)
+        if drop_block_rate > 0:
+            self.drop_block = DropBlock2d(drop_block_rate, drop_block_size, drop_block_gamma)
         self.relu = nn.ReLU(inplace=True)
         self.downsample = downsample
         self.stride = stride
@@ -145,7 +196,11 @@ class Bottleneck(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         identity = x
         out = self.relu(self.bn1(self.conv1(x)))
-        out = self.relu(self.bn2(self.conv2(out)))
+        out = self.bn2(self.conv2(out))
+        drop = getattr(self, "drop_block", None)
+        if drop is not None:
+            out = drop(out)
+        out = self.relu(out)
         blur = getattr(self, "blur", None)
         if blur is not None:
             out = blur(out)
@@ -168,15 +223,22 @@ class ResNet(nn.Module):
     ``blur_pool``: the anti-aliased ResNet (timm's resnetblurN) -- every stride-2 block down-samples with a
     :class:`BlurPool2d` behind its 3x3 conv, run at stride 1, and the stem pool becomes
     ``Sequential(MaxPool2d(3, 1, 1), BlurPool2d(64, 2))``. State-dict keys and parameter counts do not change.
+    ``drop_block_rate`` > 0 (timm's argument of the same name): every block of layer3 gets a :class:`DropBlock2d`
+    of block size 5 and gamma scale 0.25, every block of layer4 one of block size 3 and gamma scale 1.0; the sites
+    are numbered in module order (``drop_block.site``). With rate 0 the module tree is what it was.
     """
 
     def __init__(self, block: Type[Union[BasicBlock, Bottleneck]], layers: Sequence[int],
                  num_classes: int = 1000, in_channels: int = 3,
                  zero_init_residual: bool = False, groups: int = 1, width_per_group: int = 64,
-                 se_reduction: int = 0, blur_pool: bool = False):
+                 se_reduction: int = 0, blur_pool: bool = False, drop_block_rate: float = 0.0):
         super().__init__()
         if blur_pool:  # (no attribute without it)
             self.blur_pool = True
+        if not 0.0 <= drop_block_rate < 1.0:
+            raise ValueError(f"drop_block_rate must be in [0, 1), got {drop_block_rate}")
+        if drop_block_rate > 0:  # (likewise)
+            self.drop_block_rate = float(drop_block_rate)
         if se_reduction < 0:
             raise ValueError(f"se_reduction must be >= 0, got {se_reduction}")
         self.se_reduction = int(se_reduction)
@@ -194,13 +256,15 @@ class ResNet(nn.Module):
             nn.MaxPool2d(kernel_size=3, stride=1, padding=1), BlurPool2d(64, stride=2))
         self.layer1 = self._make_layer(block, 64, layers[0])
         self.layer2 = self._make_layer(block, 128, layers[1], stride=2)
-        self.layer3 = self._make_layer(block, 256, layers[2], stride=2)
-        self.layer4 = self._make_layer(block, 512, layers[3], stride=2)
+        self.layer3 = self._make_layer(block, 256, layers[2], stride=2, drop_block=(5, 0.25))
+        self.layer4 = self._make_layer(block, 512, layers[3], stride=2, drop_block=(3, 1.0))
+        for site, mod in enumerate(m for m in self.modules() if isinstance(m, DropBlock2d)):
+            mod.site = site
         self.avgpool = nn.AdaptiveAvgPool2d((1, 1))
         self.fc = nn.Linear(512 * block.expansion, num_classes)
         init_resnet_(self, zero_init_residual)
 
-    def _make_layer(self, block, planes: int, blocks: int, stride: int = 1) -> nn.Sequential:
+    def _make_layer(self, block, planes: int, blocks: int, stride: int = 1, drop_block=None) -> nn.Sequential:
         downsample = None
         if stride != 1 or self.inplanes != planes * block.expansion:
             downsample = nn.Sequential(
@@ -212,6 +276,8 @@ class ResNet(nn.Module):
             kw["se_reduction"] = self.se_reduction
         if getattr(self, "blur_pool", False):
             kw["blur_pool"] = True
+        if drop_block is not None and getattr(self, "drop_block_rate", 0.0) > 0:
+            kw.update(drop_block_rate=self.drop_block_rate, drop_block_size=drop_block[0], drop_block_gamma=drop_block[1])
         layers: List[nn.Module] = [block(self.inplanes, planes, stride, downsample, **kw)]
         self.inplanes = planes * block.expansion
         for _ in range(1, blocks):

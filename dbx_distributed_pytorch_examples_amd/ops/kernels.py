@@ -1348,6 +1348,105 @@ def blur_bn_bwd_apply(dpool, y, scale, shift, coeff, dy):
                     stream_ptr(), 1)
 
 
+# ---- DropBlock (csrc/dropblock_ops.hip) -------------------------------------------------------------------------------
+# A site behind a BN on [N, H, W, C]: ``bits`` int32 [N, H, W, C / 32] (bit c % 32 = keep), ``kept`` int64[1] (the site's
+# counter: zeroed before dropblock_mask adds to it, read on the device by the other three), ``thr`` int32[1] (the bits
+# of the uint32 seed threshold) and ``offset`` int32[1] (the Philox offset). The kernels are reached through the
+# dropblock_op / dropblock_args arguments of dropout's binding.
+# dbx::DropBlockArgs (csrc/abi.h), in order: 16 pointers, the 64-bit seed, then 8 int32
+_DB_PTRS = ("y", "d", "out", "bits", "sc", "sh", "c1", "c2", "c3", "stats", "kept", "thr", "offset")
+_DB_INTS = ("N", "H", "W", "C", "bs", "site", "nshard")
+DB_MASK, DB_FWD, DB_BWD_REDUCE, DB_BWD_APPLY = 1, 2, 3, 4
+dropblock_geometry, dropblock_threshold, dropblock_scale = (_ref.dropblock_geometry, _ref.dropblock_threshold,
+                                                            _ref.dropblock_scale)
+
+
+def dropblock_supported(C: int, H: int, W: int, block_size: int) -> bool:
+    return C >= 64 and C % 64 == 0 and H >= 1 and W >= 1 and 1 <= block_size <= _ref.DROPBLOCK_MAX_BS
+
+
+def _dropblock_launch(op: int, seed: int = 0, **f) -> None:
+    """Pack a host ``dbx::DropBlockArgs`` from tensors / ints by field name and run ``dbx_dropblock_op``."""
+    import numpy as np
+    buf = np.zeros(16 * 8 + 8 + 8 * 4, dtype=np.uint8)
+    buf[:8 * len(_DB_PTRS)].view(np.uint64)[:] = [_p(f.get(k)) for k in _DB_PTRS]
+    buf[128:136].view(np.uint64)[0] = int(seed) & ((1 << 64) - 1)
+    buf[136:136 + 4 * len(_DB_INTS)].view(np.int32)[:] = [int(f.get(k, 0)) for k in _DB_INTS]
+    C().dropout(0, 0, 0, 0, 0, 0, 1.0, 0, stream_ptr(), op, buf.ctypes.data)
+
+
+def _chk_dropblock(y, bits, kept, vecs=()) -> dict:
+    """The activation / mask pair of a DropBlock launch, checked: the size fields of its argument table."""
+    if y.dim() != 4:
+        raise ValueError(f"dropblock: expected an NHWC tensor, got shape {tuple(y.shape)}")
+    N, H, W, Cc = y.shape
+    _ref.check_dropblock(Cc, H, W, 1, N)
+    _chk(y, torch.bfloat16, "y")
+    _chk(bits, torch.int32, "bits", N * H * W * Cc // 32)
+    _chk(kept, torch.int64, "kept", 1)
+    for t, nm, n in vecs:
+        _chk(t, torch.float32, nm, n * Cc)
+    return dict(N=N, H=H, W=W, C=Cc, bs=1)  # (the block size shapes the mask alone)
+
+
+def dropblock_mask(bits, kept, thr, offset, *, block_size, seed, site):
+    """bits = the keep mask of site ``site`` on the [N, H, W, C / 32 * 32] map ``bits`` describes, drawn from
+    Philox(seed, offset[0]) with the seed threshold ``thr[0]``; ``kept[0]`` += its number of ones (the caller zeroes
+    it). Reads no activation. On the CPU: ``reference.dropblock_mask``."""
+    if bits.dim() != 4 or bits.dtype != torch.int32:
+        raise ValueError(f"bits: expected an int32 [N, H, W, C / 32] tensor, got {bits.dtype} {tuple(bits.shape)}")
+    N, H, W, Cw = bits.shape
+    _ref.check_dropblock(Cw * 32, H, W, int(block_size), N)
+    if not 0 <= int(site) <= 65535:
+        raise ValueError(f"site: expected 0..65535, got {site}")
+    if not use_native(bits):
+        b, k = _ref.dropblock_mask(N, H, W, Cw * 32, int(thr[0]) & 0xFFFFFFFF, int(block_size), int(seed),
+                                   int(offset[0]) & 0xFFFFFFFF, int(site))
+        bits.copy_(b)
+        kept += k
+        return bits
+    _chk(bits, torch.int32, "bits")
+    _chk(kept, torch.int64, "kept", 1)
+    _chk(thr, torch.int32, "thr", 1)
+    _chk(offset, torch.int32, "offset", 1)
+    _dropblock_launch(DB_MASK, seed, bits=bits, kept=kept, thr=thr, offset=offset, N=N, H=H, W=W, C=Cw * 32,
+                      bs=int(block_size), site=int(site))
+    return bits
+
+
+@_dispatch
+def dropblock_fwd(y, scale, shift, bits, kept, out):
+    """out = bf16(relu(y*scale + shift) * keep * (numel / max(kept, 1))) in one pass."""
+    dims = _chk_dropblock(y, bits, kept, ((scale, "scale", 1), (shift, "shift", 1)))
+    _chk(out, torch.bfloat16, "out", y.numel())
+    _dropblock_launch(DB_FWD, y=y, sc=scale, sh=shift, bits=bits, kept=kept, out=out, **dims)
+    return out
+
+
+@_dispatch
+def dropblock_bn_bwd_reduce(das, y, scale, shift, bits, kept, mean, invstd, stats):
+    """BN-backward reduce behind a DropBlock site: g = das * keep * scale masked by relu(y*scale + shift) > 0;
+    stats += [sum g, sum g*xhat]. g is never written."""
+    dims = _chk_dropblock(y, bits, kept, ((scale, "scale", 1), (shift, "shift", 1), (mean, "mean", 1),
+                                                      (invstd, "invstd", 1)))
+    _chk(das, torch.bfloat16, "das", y.numel())
+    nsh = _chk_stats(stats, "stats", dims["C"])
+    _dropblock_launch(DB_BWD_REDUCE, y=y, d=das, sc=scale, sh=shift, bits=bits, kept=kept, c1=mean, c2=invstd,
+                      stats=stats, nshard=nsh, **dims)
+
+
+@_dispatch
+def dropblock_bn_bwd_apply(das, y, scale, shift, bits, kept, coeff, dy):
+    """dy = k1*g + k2*y + k3 with g recomputed as in ``dropblock_bn_bwd_reduce``."""
+    dims = _chk_dropblock(y, bits, kept, ((scale, "scale", 1), (shift, "shift", 1), (coeff, "coeff", 3)))
+    _chk(das, torch.bfloat16, "das", y.numel())
+    _chk(dy, torch.bfloat16, "dy", y.numel())
+    Cc = dims["C"]
+    k = coeff.view(3, Cc)
+    _dropblock_launch(DB_BWD_APPLY, y=y, d=das, sc=scale, sh=shift, bits=bits, kept=kept, c1=k[0], c2=k[1], c3=k[2],
+                      out=dy, **dims)
+
+
 def stem_bwd_supported(C: int, K: int, stride: int, R: int, S: int) -> bool:
     """Geometry of the fused stem backward (csrc/stem_bwd.hip): 64 stem channels, <= 8x8 taps,
     pooling windows that cover a pixel at most twice per dimension."""

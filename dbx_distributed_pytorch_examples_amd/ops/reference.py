@@ -537,6 +537,90 @@ def blur_bn_bwd_apply(dpool, y, scale, shift, coeff, dy):
     dy.copy_((k[0] * g + k[1] * y.float() + k[2]).bfloat16())
 
 
+# ---- DropBlock (csrc/dropblock_ops.hip): the Philox block mask and the passes around it ----------------------------
+DROPBLOCK_MAX_BS = 7
+
+
+def dropblock_geometry(H: int, W: int, block_size: int, drop_prob: float, gamma_scale: float = 1.0):
+    """(bs, gamma) of a site on an H x W map: the block size clipped to the map and made odd, and the seed
+    probability ``gamma_scale * p * H*W / bs^2 / ((H - bs + 1) * (W - bs + 1))`` (timm's drop_block_2d), in double."""
+    bs = min(int(block_size), H, W)
+    bs -= 1 - bs % 2
+    gamma = float(gamma_scale) * float(drop_prob) * (H * W) / (bs * bs) / ((H - bs + 1) * (W - bs + 1))
+    return bs, gamma
+
+
+def dropblock_threshold(gamma: float) -> int:
+    """The uint32 a Philox word is compared with: an element is a seed iff word < thr."""
+    return max(0, min(0xFFFFFFFF, int(math.floor(gamma * 4294967296.0))))
+
+
+def dropblock_scale(numel: int, kept: int) -> float:
+    """(float)((double) numel / (double) max(kept, 1)), as the kernels form it."""
+    import numpy as np
+    return float(np.float32(float(numel) / float(max(int(kept), 1))))
+
+
+def check_dropblock(C: int, H: int, W: int, block_size: int, N: int = 1) -> None:
+    if C < 64 or C % 64 or H < 1 or W < 1 or not 1 <= block_size <= DROPBLOCK_MAX_BS or not 1 <= N <= 65535 \
+            or N * H * W * C >= 2 ** 31:
+        raise ValueError(f"the DropBlock kernels take C % 64 == 0, a block size in 1..{DROPBLOCK_MAX_BS} and at most "
+                         f"65535 images; got N={N}, C={C}, {H} x {W}, block size {block_size}")
+
+
+def dropblock_mask(N: int, H: int, W: int, C: int, thr: int, bs: int, seed: int, offset: int, site: int):
+    """The keep mask of a site as packed bits, int32 [N, H, W, C / 32] (bit c % 32 of a word = keep), and the number
+    of kept elements. Element (n, h, w, c) draws ``philox_u32(site * 2^48 + ((n*H + h)*W + w)*C + c, seed, offset)``;
+    it is a seed iff the word is below ``thr`` inside the valid interior, and a seed zeroes its bs x bs window."""
+    import numpy as np
+    bs = dropblock_geometry(H, W, bs, 0.0)[0]
+    r = bs // 2
+    idx = np.uint64(site << 48) + np.arange(N * H * W * C, dtype=np.uint64)
+    seeds = (philox_u32(idx, seed, offset) < np.uint64(thr)).reshape(N, H, W, C)
+    seeds[:, :r], seeds[:, H - r:], seeds[:, :, :r], seeds[:, :, W - r:] = False, False, False, False
+    pad = np.zeros((N, H + 2 * r, W + 2 * r, C), dtype=bool)
+    pad[:, r:r + H, r:r + W] = seeds
+    drop = np.zeros((N, H, W, C), dtype=bool)
+    for dh in range(bs):
+        for dw in range(bs):
+            drop |= pad[:, dh:dh + H, dw:dw + W]
+    keep = ~drop
+    words = (keep.reshape(N, H, W, C // 32, 32).astype(np.uint64) << np.arange(32, dtype=np.uint64)).sum(-1)
+    return torch.from_numpy(words.astype(np.uint32).view(np.int32)), int(keep.sum())
+
+
+def dropblock_unpack(bits, C: int):
+    """The packed mask as fp32 zeros and ones, [N, H, W, C]."""
+    w = bits.to(torch.int64).unsqueeze(-1) >> torch.arange(32, device=bits.device)
+    return (w & 1).reshape(*bits.shape[:3], C).float()
+
+
+def _dropblock_g(das, y, scale, shift, bits, kept):
+    m = dropblock_unpack(bits, y.shape[-1]) * dropblock_scale(y.numel(), int(kept))
+    return das.float() * m * (y.float() * scale + shift > 0)
+
+
+def dropblock_fwd(y, scale, shift, bits, kept, out):
+    m = dropblock_unpack(bits, y.shape[-1]) * dropblock_scale(y.numel(), int(kept))
+    out.copy_((torch.relu(y.float() * scale + shift) * m).bfloat16())
+    return out
+
+
+def dropblock_bn_bwd_reduce(das, y, scale, shift, bits, kept, mean, invstd, stats):
+    C = y.shape[-1]
+    g = _dropblock_g(das, y, scale, shift, bits, kept).reshape(-1, C)
+    xhat = ((y.float() - mean) * invstd).reshape(-1, C)
+    st = stats.view(-1, 2, C)
+    st[0, 0] += g.sum(0).double()
+    st[0, 1] += (g * xhat).sum(0).double()
+
+
+def dropblock_bn_bwd_apply(das, y, scale, shift, bits, kept, coeff, dy):
+    g = _dropblock_g(das, y, scale, shift, bits, kept)
+    k = coeff.view(3, y.shape[-1])
+    dy.copy_((k[0] * g + k[1] * y.float() + k[2]).bfloat16())
+
+
 def stem_bwd_fused(dpool, arg, y, scale, shift, coeff, x4, dw, ws, *, K=3, stride=2, pad=1, R=7, S=7,
                    conv_stride=2, conv_pad=3):
     """Fused stem backward = pool_bn_bwd_apply + the stem weight gradient."""

@@ -171,7 +171,8 @@ class _Native:
                                     seed=cfg.seed, grad_accum=cfg.grad_accum, ema_decay=cfg.ema_decay,
                                     ema_warmup=cfg.ema_warmup, **mix_options(cfg.data),
                                     **auto_augment_options(cfg.data), **loss_options(cfg.data),
-                                    drop_path_rate=cfg.drop_path_rate, **resample_options(cfg.data))
+                                    drop_path_rate=cfg.drop_path_rate, drop_block_rate=cfg.drop_block_rate,
+                                    **resample_options(cfg.data))
         self.ema_eval = bool(cfg.ema_eval)
         self.eval_topk, self.eval_graph = _eval_topk(cfg), bool(cfg.eval_graph)
         if rg:  # torchvision's RandomResizedCrop + flip on the original image; else Resize(shorter side to s)
@@ -403,7 +404,8 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
     torch.manual_seed(cfg.seed)
     np.random.seed(cfg.seed)
     if model is None:
-        model = build_model(cfg.model, num_classes=cfg.num_classes)
+        model = build_model(cfg.model, num_classes=cfg.num_classes,
+                            **({"drop_block_rate": cfg.drop_block_rate} if cfg.drop_block_rate > 0 else {}))
     if train_dataset is None:
         from ..data.datasets import build_dataset
         d = cfg.data
@@ -422,6 +424,11 @@ def train(cfg: Optional[TrainConfig] = None, model: Optional[torch.nn.Module] = 
             raise ValueError(f"drop_path_rate={cfg.drop_path_rate} needs the native training step (NativeTrainer, "
                              f"which gates the blocks' last BatchNorm); this run would use the "
                              f"{'frozen-backbone' if engine == 'native' else engine} engine, which drops no block")
+    if cfg.drop_block_rate > 0:  # refused, never ignored (the autograd engine runs the torch module)
+        from ..models.wrappers import FrozenBackboneClassifier
+        if isinstance(model, FrozenBackboneClassifier):
+            raise ValueError(f"drop_block_rate={cfg.drop_block_rate} needs a trained backbone; this run would use the "
+                             f"frozen-backbone engine, which drops nothing")
     if cfg.data.ragged:  # refused, never ignored
         from ..models.wrappers import FrozenBackboneClassifier
         if engine != "native" or isinstance(model, FrozenBackboneClassifier):
