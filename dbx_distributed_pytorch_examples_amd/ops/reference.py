@@ -146,7 +146,7 @@ def conv_wgrad(dy, x, dw, ws, *, R, S, stride, pad, in_scale=None, in_shift=None
     g = g.permute(0, 2, 3, 1) * scale  # KRSC
     if stem and out_krsc is not None:  # the real input channels only (x is padded to 4)
         icr = out_krsc.numel() // (OC * R * S)
-        out_krsc.copy_((g[..., :icr].reshape(-1) + (out_krsc if accumulate else 0)))
+        out_krsc.copy_((g[..., :icr].reshape(out_krsc.shape) + (out_krsc if accumulate else 0)))
         return out_krsc
     if stem:
         full = torch.zeros(OC, 8, 8, 4, dtype=torch.float32, device=dy.device)
